@@ -5,12 +5,13 @@ One step = one iteration of the reference batch loop (Retrieval/ATMS_retrieval.p
 already resident in HBM: ATMS forward (train mode, dropout + batch-stat BatchNorm), image + text InfoNCE (0.99/0.01),
 backward, AdamW, and the running train-accuracy GEMM + argmax vs 1654 class embeddings.  Nothing is skipped or cached.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 N > 1: one process per GPU over RCCL; weak scaling (256 samples per GPU, global batch 256*N); ClipLoss all-gathers the
 embeddings so every rank scores against the GLOBAL negatives, the flat gradient buffer is all-reduced once per step.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the headline; --full adds the roofline object (instrumented
+steps, per-launch timing inside the timed region), the collective log of several ranks, the secondary measurements and the CPU baseline.
 """
 import argparse
 import json
@@ -154,6 +155,8 @@ def algorithmic_flops(name, desc, B):
 
 
 TIME_EVERY = 8
+RAMP_STEPS = 600
+DUMP_MAX_ROWS = 4096
 
 
 def family_of(name, desc):
@@ -537,18 +540,41 @@ def _sec_end_to_end():
         shutil.rmtree(root, ignore_errors=True)
 
 
+def dump_outputs(out_dir, feats, loss, correct, model):
+    """What the timed path (retrieval.contrastive_step) handed its caller in the last timed step, one DIR/<name>.npy per array: the embeddings
+    it returned (a fixed, seeded sample of DUMP_MAX_ROWS rows above that batch size), that step's loss, the running train-accuracy count, and
+    every entry of the model's state_dict as the optimizer left it (18 MB at B = 256).  Floating arrays as float32, integer ones as float64.
+    Not the attention's key-projection bias: softmax over keys is invariant to it, so its gradient is zero up to rounding and AdamW turns that
+    rounding noise into lr-sized steps -- its value differs from run to run by ~2 % of its size (tests/test_dp_gpu.py skips it too)."""
+    os.makedirs(out_dir, exist_ok=True)
+    feats = feats.detach()
+    if feats.shape[0] > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(feats.shape[0], DUMP_MAX_ROWS, replace=False))
+        feats = feats[torch.from_numpy(rows).to(feats.device)]
+    arrays = {"embeddings": feats, "loss": loss, "train_correct": correct}
+    arrays.update({"state." + k: v for k, v in model.state_dict().items() if not k.endswith("key_projection.bias")})
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="timed steps")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256, help="samples per GPU (BASELINE configs[1]: 256)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (other SURVEY section 8 rows)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the roofline object (instrumented steps, per-launch "
+                    "timing inside the timed region), the collective log of several ranks, the secondary measurements and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one handed its caller as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary measurements (other SURVEY section 8 rows)")
     ap.add_argument("--breakdown", action="store_true", help="time every kernel of the fwd/bwd plans with HIP events and print a table")
     ap.add_argument("--roofline-kernel", default="auto", help="kernel family for the roofline object: gemm_bf16x3, gemm_f32 or an op name such as "
                     "eegclip_sconv_fwd (auto = the family with the largest total time)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.breakdown:
         os.environ["EEGCLIP_STEP_PLAN"] = "0"       # every op is timed through the encoder's own plans (the step plan replays the same launches)
 
@@ -564,7 +590,7 @@ def main():
 
     def step(i):
         d = pool[i % len(pool)]
-        retrieval.contrastive_step(model, opt, d["eeg"], 1, d["img"], d["txt"], d["labels"], classes, loss_acc, correct)
+        return retrieval.contrastive_step(model, opt, d["eeg"], 1, d["img"], d["txt"], d["labels"], classes, loss_acc, correct)
 
     def barrier():
         if world > 1:
@@ -572,14 +598,12 @@ def main():
         torch.cuda.synchronize()
 
     # plan building + clock ramp (untimed, before the official warm-up): the first steps compile nothing but build the launch plans,
-    # and a cold GPU needs a few hundred milliseconds of load to reach its sustained clocks
-    t_ramp = time.perf_counter()
-    i_ramp = 0
-    # (several ranks: every step holds collectives, so all ranks must run the SAME number of steps -- a fixed count, not a time-based one)
-    while (time.perf_counter() - t_ramp < 0.4 or i_ramp < 3) if world == 1 else i_ramp < 48:
+    # and a cold GPU needs a few hundred milliseconds of load to reach its sustained clocks (RAMP_STEPS: ~0.4 s of steps on one MI355X).
+    # A fixed count, not a time-based one: with several ranks every step holds collectives, so all ranks must run the SAME number of steps, and
+    # the model state the timed steps start from (--dump-outputs) must not depend on how fast the build runs
+    for i_ramp in range(RAMP_STEPS if world == 1 else 48):
         step(i_ramp)
-        i_ramp += 1
-        if i_ramp % 16 == 0:
+        if (i_ramp + 1) % 16 == 0:
             torch.cuda.synchronize()
     torch.cuda.synchronize()
     # what the product's own loops do before their first step (retrieval.train_model, Pipe.train): one full collection + gc.freeze(), so that no
@@ -587,61 +611,65 @@ def main():
     retrieval.settle_gc()
     for i in range(args.warmup):
         step(i)
-    eng = model._engine()
-    plans = {k: v for k, v in eng.plans.items()}
-    # ---- the dominant kernel: 3 instrumented single-stream steps (outside the headline clock) time every launch on its own; launches are
-    # grouped into families (all GEMM launches of one arithmetic are one kernel template) and the family with the largest total time is
-    # the one the roofline object describes.  ALL its launches are then timed live inside the timed region (HIP events on the stream each
-    # launch goes to -- the backward overlaps two streams there, which stretches per-launch durations: both figures are reported).
-    # (the single-submission step plan -- step_plan.py -- replays the very same launches; the instrumented steps go launch by launch through the
-    #  encoder's own plans, whose ops carry the timing hooks)
-    os.environ["EEGCLIP_STEP_PLAN_OFF_FOR_BENCH"] = os.environ.get("EEGCLIP_STEP_PLAN", "1")
-    os.environ["EEGCLIP_STEP_PLAN"] = "0"
-    for k, pl in plans.items():
-        pl.use_side_stream = False
-        pl.time_ops(range(len(pl.ops)))
-    for i in range(3):
-        step(i)
-    single = {}                                   # (plan key, op index) -> mean ms on one stream
-    for k, pl in plans.items():
-        for idx, v in pl.timings_ms().items():
-            single[(k, idx)] = float(np.mean(v))
-        pl.time_ops([])
-        pl.use_side_stream = True
-    os.environ["EEGCLIP_STEP_PLAN"] = os.environ.pop("EEGCLIP_STEP_PLAN_OFF_FOR_BENCH")
-    step(0)                                       # (back on the step plan, if the configuration has one)
-    sp = next(iter(retrieval.step_plans_of(model)), None)
-    fam_ops, fam_ms = {}, {}
-    for (k, idx), ms in single.items():
-        name = plans[k].ops[idx][2]
-        d = _desc_of(plans[k], idx)
-        if algorithmic_cost(name, d, B) is None:
-            continue
-        fam = family_of(name, d)
-        fam_ops.setdefault(fam, []).append((k, idx))
-        fam_ms[fam] = fam_ms.get(fam, 0.0) + ms
-    dominant = max(fam_ms, key=fam_ms.get) if args.roofline_kernel == "auto" else args.roofline_kernel
-    if args.breakdown:
+    instrument = args.full or args.breakdown      # (a plain run: set-up, warm-up and the timed steps, nothing else)
+    if instrument:
+        eng = model._engine()
+        plans = {k: v for k, v in eng.plans.items()}
+        # ---- the dominant kernel: 3 instrumented single-stream steps (outside the headline clock) time every launch on its own; launches are
+        # grouped into families (all GEMM launches of one arithmetic are one kernel template) and the family with the largest total time is
+        # the one the roofline object describes.  ALL its launches are then timed live inside the timed region (HIP events on the stream each
+        # launch goes to -- the backward overlaps two streams there, which stretches per-launch durations: both figures are reported).
+        # (the single-submission step plan -- step_plan.py -- replays the very same launches; the instrumented steps go launch by launch through the
+        #  encoder's own plans, whose ops carry the timing hooks)
+        os.environ["EEGCLIP_STEP_PLAN_OFF_FOR_BENCH"] = os.environ.get("EEGCLIP_STEP_PLAN", "1")
+        os.environ["EEGCLIP_STEP_PLAN"] = "0"
         for k, pl in plans.items():
             pl.use_side_stream = False
             pl.time_ops(range(len(pl.ops)))
-    else:
-        by_plan = {}
-        for k, idx in fam_ops.get(dominant, []):
-            by_plan.setdefault(k, []).append(idx)
-        # every launch of the family is timed on every TIME_EVERY-th step of the timed region (two HIP events per launch: ~40 per step for the GEMM
-        # family, ~0.1 ms of a 1.2 ms step if recorded on every step -- instrumentation the product does not carry; 3+ sampled steps x 20 launches)
-        every = TIME_EVERY if args.steps >= 2 * TIME_EVERY else 1
-        if sp is not None:                        # the step plan holds the encoder plans' ops at fixed offsets
-            sp.pl.time_ops([sp.index_of(k[0], i) for k, idxs in by_plan.items() for i in idxs], every=every)
+        for i in range(3):
+            step(i)
+        single = {}                                   # (plan key, op index) -> mean ms on one stream
+        for k, pl in plans.items():
+            for idx, v in pl.timings_ms().items():
+                single[(k, idx)] = float(np.mean(v))
+            pl.time_ops([])
+            pl.use_side_stream = True
+        os.environ["EEGCLIP_STEP_PLAN"] = os.environ.pop("EEGCLIP_STEP_PLAN_OFF_FOR_BENCH")
+        step(0)                                       # (back on the step plan, if the configuration has one)
+        sp = next(iter(retrieval.step_plans_of(model)), None)
+        fam_ops, fam_ms = {}, {}
+        for (k, idx), ms in single.items():
+            name = plans[k].ops[idx][2]
+            d = _desc_of(plans[k], idx)
+            if algorithmic_cost(name, d, B) is None:
+                continue
+            fam = family_of(name, d)
+            fam_ops.setdefault(fam, []).append((k, idx))
+            fam_ms[fam] = fam_ms.get(fam, 0.0) + ms
+        dominant = max(fam_ms, key=fam_ms.get) if args.roofline_kernel == "auto" else args.roofline_kernel
+        if args.breakdown:
+            for k, pl in plans.items():
+                pl.use_side_stream = False
+                pl.time_ops(range(len(pl.ops)))
         else:
-            for k, idxs in by_plan.items():
-                plans[k].time_ops(idxs, every=every)
+            by_plan = {}
+            for k, idx in fam_ops.get(dominant, []):
+                by_plan.setdefault(k, []).append(idx)
+            # every launch of the family is timed on every TIME_EVERY-th step of the timed region (two HIP events per launch: ~40 per step for the GEMM
+            # family, ~0.1 ms of a 1.2 ms step if recorded on every step -- instrumentation the product does not carry; 3+ sampled steps x 20 launches)
+            every = TIME_EVERY if args.steps >= 2 * TIME_EVERY else 1
+            if sp is not None:                        # the step plan holds the encoder plans' ops at fixed offsets
+                sp.pl.time_ops([sp.index_of(k[0], i) for k, idxs in by_plan.items() for i in idxs], every=every)
+            else:
+                for k, idxs in by_plan.items():
+                    plans[k].time_ops(idxs, every=every)
+    else:
+        sp = next(iter(retrieval.step_plans_of(model)), None)
 
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        feats = step(i)
     t_enq = time.perf_counter() - t0          # host time to ENQUEUE the steps (no sync inside a step): must stay below the GPU time
     barrier()
     dt = time.perf_counter() - t0
@@ -651,6 +679,8 @@ def main():
         dt = float(tmax)
     ms_per_step = 1e3 * dt / args.steps
     value = world * B * args.steps / dt
+    if args.dump_outputs and rank == 0:       # (before anything else launches: the roofline's extra GEMM launches reuse the plans' buffers)
+        dump_outputs(args.dump_outputs, feats, loss_acc[-1], correct, model)
     final_loss = float(retrieval.running_loss(loss_acc)) / max(1, len(loss_acc))
 
     roof = None
@@ -670,7 +700,7 @@ def main():
             print(f"# per-kernel HIP-event breakdown (ms/step, mean over {args.steps} steps); sum of kernels = {tot:.3f} ms, step = {ms_per_step:.3f} ms", file=sys.stderr)
             for ms, ph, idx, tag in rows:
                 print(f"#  {ms:8.4f} ms  {100 * ms / tot:5.1f}%  {ph}{idx:02d}  {tag}", file=sys.stderr)
-    elif dominant in fam_ops:
+    elif instrument and dominant in fam_ops:
         ops = fam_ops[dominant]
         live = {}
         if sp is not None:
@@ -787,19 +817,20 @@ def main():
 
     distributed = None
     if world > 1:
-        # what the run actually was (the driver's first multi-GPU line must show "RCCL saw N ranks") + where the step's communication time goes:
-        # 5 extra instrumented steps AFTER the timed region, an event pair on the compute stream around every collective (async ones: issue .. wait())
+        # what the run actually was (the driver's first multi-GPU line must show "RCCL saw N ranks") + with --full where the step's communication time
+        # goes: 5 extra instrumented steps AFTER the timed region, an event pair on the compute stream around every collective (async ones: issue .. wait())
         distributed = {"backend": torch.distributed.get_backend(), "world_size": torch.distributed.get_world_size(),
                        "rccl_version": ".".join(str(v) for v in torch.cuda.nccl.version()) if torch.distributed.get_backend() == "nccl" else None,
                        "devices_visible": torch.cuda.device_count(), "sync_batchnorm": bool(model.sync_batchnorm),
                        "loss_mode": {"local_loss": model.loss_func.local_loss, "gather_with_grad": model.loss_func.gather_with_grad}}
-        log = _CollectiveLog()
-        with log:
-            for i in range(5):
-                step(i)
-            torch.cuda.synchronize()
-        distributed["collectives"] = log.summary(5)
-        barrier()
+        if args.full:
+            log = _CollectiveLog()
+            with log:
+                for i in range(5):
+                    step(i)
+                torch.cuda.synchronize()
+            distributed["collectives"] = log.summary(5)
+            barrier()
 
     out = {
         "metric": "EEG-CLIP contrastive train samples/sec (global batch)", "value": round(value, 1), "unit": "samples/s",
@@ -821,11 +852,11 @@ def main():
     }
     if distributed is not None:
         out["distributed"] = distributed
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         del model, opt, pool
         torch.cuda.empty_cache()
         out["secondary"] = secondary()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(B)
     if rank == 0:
         print(json.dumps(out))

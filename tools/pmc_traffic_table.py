@@ -39,7 +39,7 @@ def main(path, batch):
             if cyc:
                 fams[fam]["mfma_busy_frac"] = round(busy / cyc, 4)
     out = {"batch": batch,
-           "source": f"{path}: rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --steps 12 --warmup 3 "
+           "source": f"{path}: rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --steps 12 --warmup 3 --full "
                      "--no-secondary --no-cpu-baseline (tools/final_profiles.sh); hbm_bytes = (2 FETCH_SIZE + WRITE_SIZE) KiB per launch (gfx950 "
                      "FETCH_SIZE correction of MI355X_MICROARCH.md), launch-weighted mean over the family's kernels (tools/pmc_summary.py, this script)",
            "families": fams}

@@ -6,7 +6,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 F='RCCL\|HIP version\|ROCm version\|Hostname\|Librccl\|amdgpu.ids'
 # the bench line first, on the fresh box (its `traffic` fields then come from the committed PMC table of the previous evidence run of the same kernels)
-timeout 400 python bench.py --steps 50 --warmup 10 > $out/bench.json 2> $out/bench.err < /dev/null
+timeout 400 python bench.py --steps 50 --warmup 10 --full > $out/bench.json 2> $out/bench.err < /dev/null
 cut -c1-300 $out/bench.json
 export SKIP_BENCH=1
 (timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | grep -v "$F" | tail -15) > $out/tests_gpu.log 2>&1
