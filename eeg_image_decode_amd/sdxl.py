@@ -13,10 +13,14 @@ self-contained:
                                                      per-step update of the latents (+ classifier-free-guidance mix) is one kernel launch.
 * generate_ip_adapter_embeds(pipe, ...)              the sampling loop with the reference's signature and order of operations
                                                      (custom_pipeline.py:244-385), plus the img2img start of custom_pipeline_low_level.py:331-389.
-* SDXLShapedUNet                                     a randomly initialised STAND-IN for the UNet with SDXL-base's cross-attention stack:
-                                                     70 transformer positions at the real shapes (10 x (HW/4, 640 ch, 10 heads), 60 x (HW/16,
+* self_attention(...) / HIPAttnProcessor             the UNet self-attention (attn1) as a flash-style kernel (csrc/self_attn.hip: K / V streamed
+                                                     through LDS, no T x T score matrix); the processor runs q / k / v as ONE fused GEMM and
+                                                     to_out as one more (csrc/gemm16.hip).  Drop-in for diffusers' AttnProcessor2_0 on attn1.
+* SDXLShapedUNet                                     a randomly initialised STAND-IN for the UNet with SDXL-base's attention stack: 70
+                                                     transformer positions at the real shapes (10 x (HW/4, 640 ch, 10 heads), 60 x (HW/16,
                                                      1280 ch, 20 heads)), time / added-condition embedding, 2 x 2 patch merges between the
-                                                     resolutions.  It has NO self-attention, ResNet blocks or trained weights: it exists so that
+                                                     resolutions.  Self-attention (attn1) at every position is optional (self_attention=True);
+                                                     it has NO ResNet blocks, LayerNorms, feed-forwards or trained weights: it exists so that
                                                      the loop, the schedulers and the attention kernels run and are measured end to end.
 * StandInSDXLPipeline / Generator4Embeds             the wrapper (custom_pipeline.py:456-492).  With diffusers + checkpoints it drives the real
                                                      pipeline; offline it drives the stand-in and returns LATENTS (there is no VAE to decode).
@@ -208,6 +212,135 @@ def install_cross_attention_processors(unet, scale=1.0):
     return unet
 
 
+def _row_layout(t, name):
+    """(B, T, C) view -> (tensor, row stride in elements) as csrc/self_attn.hip addresses it: unit column stride, sample b's rows from b * T * ld.
+    Column slices of a fused (B, T, 3C) projection qualify as they are; anything else is made contiguous first."""
+    B, T, C = t.shape
+    ld = t.stride(1) if T > 1 else (t.stride(0) if B > 1 else C)
+    if t.stride(2) != 1 or (B > 1 and t.stride(0) != T * ld) or ld < C or ld % 8 or t.data_ptr() % 16:
+        if name == "out":
+            raise EegclipError("self_attention: `out` must be (B, T, C) rows with unit column stride, a row stride that is a multiple of 8 and a "
+                               "16-byte aligned base")
+        t = t.contiguous()
+        ld = C
+    return t, ld
+
+
+def self_attention(q, k, v, heads, scale=None, out=None):
+    """softmax(scale * q k^T) v per head of 64 (flash-style, csrc/self_attn.hip: no T x T buffer).  q (B, Tq, C), k / v (B, Tk, C), C = heads * 64,
+    fp16 or bf16; the three may be column slices of one fused (B, T, 3C) projection (consumed in place).  scale defaults to 1/8 (diffusers'
+    attn.scale).  Returns `out` (B, Tq, C), which may be given."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        require_cuda(t, n)
+    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise EegclipError(f"self_attention runs in fp16 or bf16 with one dtype for q, k, v (got {q.dtype}, {k.dtype}, {v.dtype})")
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise EegclipError("self_attention takes (B, T, C) tensors")
+    B, Tq, C = q.shape
+    Tk = k.shape[1]
+    if C != heads * 64:
+        raise EegclipError(f"head_dim must be 64 (C={C}, heads={heads})")
+    if tuple(k.shape) != (B, Tk, C) or tuple(v.shape) != (B, Tk, C):
+        raise EegclipError(f"self_attention: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
+    if B * Tq * Tk == 0:
+        raise EegclipError("self_attention: empty input")
+    q, ldq = _row_layout(q, "q")
+    k, ldk = _row_layout(k, "k")
+    v, ldv = _row_layout(v, "v")
+    if out is None:
+        out = torch.empty(B, Tq, C, dtype=q.dtype, device=q.device)
+    elif tuple(out.shape) != (B, Tq, C) or out.dtype != q.dtype or out.device != q.device:
+        raise EegclipError(f"self_attention: out {tuple(out.shape)} {out.dtype} does not match ({B}, {Tq}, {C}) {q.dtype}")
+    out, ldo = _row_layout(out, "out")
+    scale = 1.0 / math.sqrt(64) if scale is None else float(scale)
+    check(lib().eegclip_self_attn_fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, B, Tq, Tk, heads, 64, scale,
+                                      _dt(q), _stream()), "self_attn_fwd")
+    return out
+
+
+class HIPAttnProcessor:
+    """Self-attention (attn1) processor with diffusers' AttnProcessor2_0 call signature and arithmetic: q / k / v as ONE linear16 launch on the
+    concatenated (3C, C) weight, one self_attention launch, to_out[0] as one linear16 with its bias and (attn.residual_connection) the residual
+    as the GEMM's residual operand, then / attn.rescale_output_factor.  3-D (B, T, C) and 4-D (B, C, H, W) inputs.  With encoder_hidden_states
+    (a cross-attention) K and V come from them through separate GEMMs.  Masks, group_norm / spatial_norm and head dims other than 64 raise: this
+    processor issues no library GEMM and has no fallback.
+
+    The concatenated weight is cached per processor (one processor per layer: it costs the layer's 3 C^2 projection weights once more) and rebuilt
+    when any of to_q / to_k / to_v's weight or bias is replaced (identity) or edited in place (_version)."""
+
+    def __init__(self):
+        self._qkv = None
+
+    @staticmethod
+    def _params(attn):
+        return [attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, attn.to_q.bias, attn.to_k.bias, attn.to_v.bias]
+
+    def _fused_qkv(self, attn):
+        ps = self._params(attn)
+        # identity + version decide; the address is compared as well so that a `.data =` swap (same object) cannot serve stale weights
+        key = tuple((id(p), p._version, p.data_ptr()) if p is not None else None for p in ps)
+        c = self._qkv
+        if c is not None and c[0] == key and all(a is b for a, b in zip(c[1], ps)):
+            return c[2], c[3]
+        w = torch.cat([p.detach() for p in ps[:3]], 0).contiguous()
+        b = None
+        if any(p is not None for p in ps[3:]):
+            b = torch.cat([p.detach() if p is not None else torch.zeros(ps[i].shape[0], dtype=w.dtype, device=w.device)
+                           for i, p in enumerate(ps[3:])], 0).contiguous()
+        self._qkv = (key, ps, w, b)                                     # (holds the parameters themselves: their ids cannot be recycled)
+        return w, b
+
+    @staticmethod
+    def _lin(layer_weight, x, bias=None, residual=None):
+        if layer_weight.shape[0] % 128 or layer_weight.shape[1] % 64 or layer_weight.dtype != x.dtype:
+            raise EegclipError(f"projection {tuple(layer_weight.shape)} {layer_weight.dtype} is outside the 16-bit GEMM's shapes (N % 128, K % 64, "
+                               "dtype of the activations); this processor issues no library GEMM")
+        return linear16(x, layer_weight, bias, residual)
+
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, *args, **kwargs):
+        if attention_mask is not None:
+            raise EegclipError("HIPAttnProcessor: attention masks are not supported (SDXL's self-attention has none)")
+        if getattr(attn, "group_norm", None) is not None or getattr(attn, "spatial_norm", None) is not None:
+            raise EegclipError("HIPAttnProcessor: attn.group_norm / attn.spatial_norm are not supported (SDXL's UNet transformer blocks set neither)")
+        heads = attn.heads
+        inner = attn.to_q.weight.shape[0]
+        if inner != heads * 64:
+            raise EegclipError(f"HIPAttnProcessor: head_dim must be 64 (inner dim {inner}, {heads} heads)")
+        shape4 = hidden_states.shape if hidden_states.dim() == 4 else None
+        if shape4 is not None:
+            b, c, hh, ww = shape4
+            hidden_states = hidden_states.view(b, c, hh * ww).transpose(1, 2)
+        residual = hidden_states
+        if encoder_hidden_states is None:
+            w, bias = self._fused_qkv(attn)
+            qkv = self._lin(w, hidden_states, bias)                     # (B, T, 3C): consumed in place by the kernel
+            q, k, v = qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:]
+        else:
+            q = self._lin(attn.to_q.weight, hidden_states, attn.to_q.bias)
+            e = encoder_hidden_states
+            if getattr(attn, "norm_cross", None):
+                e = attn.norm_encoder_hidden_states(e)
+            e = e.to(q.dtype)
+            k = self._lin(attn.to_k.weight, e, attn.to_k.bias)
+            v = self._lin(attn.to_v.weight, e, attn.to_v.bias)
+        o = self_attention(q, k, v, heads, scale=getattr(attn, "scale", None))
+        res = residual if getattr(attn, "residual_connection", False) else None
+        out = self._lin(attn.to_out[0].weight, o, attn.to_out[0].bias, res)
+        out = attn.to_out[1](out)
+        if shape4 is not None:
+            out = out.transpose(-1, -2).reshape(shape4)
+        rescale = getattr(attn, "rescale_output_factor", 1.0)
+        return out / rescale if rescale != 1.0 else out
+
+
+def install_self_attention_processors(unet):
+    """Swap every self-attention (attn1) processor of a diffusers UNet2DConditionModel for a HIPAttnProcessor (one per layer) and keep the others;
+    composes with install_cross_attention_processors in either order."""
+    procs = {name: (HIPAttnProcessor() if ".attn1." in name else old) for name, old in unet.attn_processors.items()}
+    unet.set_attn_processor(procs)
+    return unet
+
+
 # ---------------------------------------------------------------------------------------------------------------------- schedulers
 def _scaled_linear_alphas_cumprod(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012):
     betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float64) ** 2          # SDXL: "scaled_linear"
@@ -343,12 +476,32 @@ class _AttnSlot(nn.Module):
         self.to_out_bias = nn.Parameter(torch.zeros(dim, dtype=dtype), requires_grad=False)
 
 
+class _SelfAttnSlot(nn.Module):
+    """the parameters of one self-attention (attn1) position: q / k / v stacked as one (3 dim, dim) weight, the output projection + bias"""
+
+    def __init__(self, dim, n_layers_total, dtype, gen):
+        super().__init__()
+        self.heads = dim // 64
+        g = lambda *s, scale: nn.Parameter((torch.randn(*s, generator=gen) * scale).to(dtype), requires_grad=False)
+        self.to_qkv = g(3 * dim, dim, scale=dim ** -0.5)
+        # 1 / n (not 1 / sqrt(n) as for attn2): this update grows with h itself, and without the LayerNorms of a real block a larger gain makes
+        # the stand-in's noise prediction, and so the latents, grow by a constant factor per denoising step
+        self.to_out = g(dim, dim, scale=dim ** -0.5 / n_layers_total)
+        self.to_out_bias = nn.Parameter(torch.zeros(dim, dtype=dtype), requires_grad=False)
+
+
 class SDXLShapedUNet(nn.Module):
     """Stand-in with SDXL-base's cross-attention stack (see the module docstring: NOT the SDXL UNet).  forward() has the call signature the
     pipeline uses (custom_pipeline.py:365-373).  Latents (B, 4, L, L): stage 1 works on (L/2)^2 tokens of 640 channels (10 heads), stage 2 on
-    (L/4)^2 tokens of 1280 channels (20 heads); layers per stage default to SDXL-base's transformer counts (4 + 20 down, 10 mid, 30 + 6 up)."""
+    (L/4)^2 tokens of 1280 channels (20 heads); layers per stage default to SDXL-base's transformer counts (4 + 20 down, 10 mid, 30 + 6 up).
 
-    def __init__(self, stage_layers=(4, 20, 10, 30, 6), cross_attention_dim=2048, ip_tokens=4, ip_scale=1.0, dtype=torch.float16, seed=0):
+    self_attention=True: every position first runs h = h + attn1(h) (fused q / k / v GEMM, csrc/self_attn.hip, output GEMM with the residual),
+    then the cross-attention, in diffusers' BasicTransformerBlock order; the LayerNorms before both are omitted, as they are for attn2.  The
+    extra weights (`self_slots`) come from their own generator seeded from `seed`: every other parameter is the default model's.  The default
+    (False) builds and runs exactly the model without them."""
+
+    def __init__(self, stage_layers=(4, 20, 10, 30, 6), cross_attention_dim=2048, ip_tokens=4, ip_scale=1.0, dtype=torch.float16, seed=0,
+                 self_attention=False):
         super().__init__()
 
         class _C:
@@ -382,6 +535,10 @@ class SDXLShapedUNet(nn.Module):
         self.image_ln_w = nn.Parameter(torch.ones(cross_attention_dim, dtype=torch.float32), requires_grad=False)
         self.image_ln_b = nn.Parameter(torch.zeros(cross_attention_dim, dtype=torch.float32), requires_grad=False)
         torch.random.set_rng_state(gen_state)
+        self.self_attention = bool(self_attention)
+        if self.self_attention:
+            sgen = torch.Generator().manual_seed(seed + 0x5E1F)
+            self.self_slots = nn.ModuleList([_SelfAttnSlot(d, n_total, dtype, sgen) for d, n in zip(self.stage_dims, stage_layers) for _ in range(n)])
         self._kv = None
 
     @property
@@ -458,6 +615,12 @@ class SDXLShapedUNet(nn.Module):
         def run(n_layers, h):
             for _ in range(n_layers):
                 i = next(it)
+                if self.self_attention:
+                    sa = self.self_slots[i]
+                    C = h.shape[-1]
+                    qkv = linear16(h, sa.to_qkv)                                              # (B, T, 3C): q / k / v read in place
+                    a = self_attention(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], sa.heads)
+                    h = linear16(a, sa.to_out, sa.to_out_bias, h)
                 s = self.slots[i]
                 k, v, kip, vip = kv[i]
                 a = cross_attention(linear16(h, s.to_q), k, v, s.heads, kip, vip, self.ip_scale)
@@ -704,11 +867,13 @@ class Generator4Embeds:
                                                     low_level_image=self.low_level_image, low_level_latent=self.low_level_latent).images[0]
 
 
-def bench_sampling_loop(images=8, steps=50, latent=128, guidance_scale=5.0, dtype=torch.float16):
+def bench_sampling_loop(images=8, steps=50, latent=128, guidance_scale=5.0, dtype=torch.float16, self_attention=False):
     """BASELINE configs[4]: 50-step DDIM sampling of `images` images per GPU with classifier-free guidance on the SDXL-shaped stand-in (1024 px:
-    128 x 128 latents, 4096 / 1024 tokens).  Returns a dict for bench.py's `secondary` object."""
+    128 x 128 latents, 4096 / 1024 tokens).  Returns a dict for bench.py's `secondary` object.  self_attention=True: the stand-in with attn1 at
+    every position (the FLOP count then includes its q / k / v / out GEMMs and Q K^T + P V over all tokens)."""
     import time
-    pipe = StandInSDXLPipeline(SDXLShapedUNet(dtype=dtype), DDIMScheduler(), device="cuda", dtype=dtype, default_sample_size=latent)
+    pipe = StandInSDXLPipeline(SDXLShapedUNet(dtype=dtype, self_attention=self_attention), DDIMScheduler(), device="cuda", dtype=dtype,
+                               default_sample_size=latent)
     emb = torch.randn(images, 1024, device="cuda", dtype=dtype)
     gen = torch.Generator(device="cuda").manual_seed(0)
     pipe.generate_ip_adapter_embeds(prompt="", ip_adapter_embeds=emb, num_inference_steps=2, guidance_scale=guidance_scale, generator=gen)      # warm-up
@@ -722,7 +887,11 @@ def bench_sampling_loop(images=8, steps=50, latent=128, guidance_scale=5.0, dtyp
     flops = 0.0
     for d, n, tok in zip(pipe.unet.stage_dims, pipe.unet.stage_layers, [(latent // 2) ** 2, (latent // 4) ** 2, (latent // 4) ** 2, (latent // 4) ** 2, (latent // 2) ** 2]):
         flops += n * (2 * 2.0 * B * tok * d * d + 4.0 * B * tok * 81 * d)            # to_q + to_out GEMMs, QK^T + PV over 77 + 4 tokens
+        if self_attention:
+            flops += n * (4 * 2.0 * B * tok * d * d + 4.0 * B * tok * tok * d)       # fused q/k/v + to_out GEMMs, QK^T + PV over all tokens
+    layers = (f"{n_layers} self-attention + {n_layers} cross-attention positions with IP-Adapter branch; no ResNets / trained weights" if self_attention
+              else f"{n_layers} cross-attention positions with IP-Adapter branch; no self-attention / ResNets / trained weights")
     return {"stand_in": True, "workload": f"configs[4] shape: {steps}-step DDIM, {images} images x CFG pair, {latent * 8} px ({latent}x{latent} latents), SDXL-SHAPED STAND-IN "
-                        f"UNet ({n_layers} cross-attention positions with IP-Adapter branch; no self-attention / ResNets / trained weights)",
+                        f"UNet ({layers})",
             "steps": steps, "seconds": round(dt, 3), "ms_per_step": round(1e3 * dt / steps, 2), "images_per_s": round(images / dt, 2),
             "attention_stack_TFLOPs": round(flops * steps / dt / 1e12, 1), "finite": bool(torch.isfinite(out.float()).all())}

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 11
+#define EEGCLIP_ABI_VERSION 12
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -430,6 +430,18 @@ int eegclip_logits_bf16(const void* a_bf16, const void* b_bf16, float* c, int M,
  * head_dim must be 64, S and S_ip <= 128, pointers 16-byte aligned. */
 int eegclip_cross_attn_fwd(const void* q, const void* k, const void* v, const void* k_ip, const void* v_ip, void* out, int B, int HW, int heads,
                            int head_dim, int S, int S_ip, float ip_scale, int dtype, void* stream);
+
+/* ---- SDXL UNet self-attention (attn1), flash-style (call site Generation/custom_pipeline.py:365-373, the UNet call; arithmetic = diffusers
+ * 0.30.0 AttnProcessor2_0, restated -- parity unpinned):
+ *   out[b, i, 64h .. 64h+63] = sum_j softmax_j(scale * q[b,i,h] . k[b,j,h]) v[b,j,h]          i < Tq, j < Tk, h < heads
+ * Row i of sample b of q starts at q + (b * Tq + i) * ldq (k, v: Tk rows, ldk / ldv; out: Tq rows, ldo); head h is columns [64h, 64h + 64).
+ * Strides in elements: a fused QKV projection (B*T, 3C) is consumed in place with ldq = ldk = ldv = 3C and bases offset by 0 / C / 2C.
+ * 16-bit I/O (dtype), fp32 scores / softmax / accumulation; no T x T buffer.  Any Tq, Tk >= 1 (Tq != Tk: long-sequence cross-attention);
+ * scale > 0 (diffusers: attn.scale = 1/8).  Writes only rows < Tq, columns [0, heads*64) of out.
+ * head_dim must be 64, strides multiples of 8 and >= heads*64, pointers 16-byte aligned; _supported() checks head_dim and strides alone. */
+int eegclip_self_attn_supported(int head_dim, long long ldq, long long ldk, long long ldv, long long ldo);
+int eegclip_self_attn_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B,
+                          int Tq, int Tk, int heads, int head_dim, float scale, int dtype, void* stream);
 
 /* ---- retrieval readouts.  ATMS_retrieval.py:246 (argmax), :320 (top-5).  ties -> lowest index; out_idx: int64 (rows, k), k <= 8 */
 int eegclip_topk_rows(const float* X, int rows, int cols, long long ld, int k, const float* scale /* device scalar or NULL: rank by scale*x */,
