@@ -81,7 +81,8 @@ class Conv16Desc(C.Structure):
     _fields_ = [("in_", C.c_void_p), ("W", C.c_void_p), ("out", C.c_void_p), ("bias", C.c_void_p), ("residual", C.c_void_p),
                 ("N", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int), ("Cin", C.c_int), ("in_pad", C.c_int),
                 ("Ho", C.c_int), ("Wo", C.c_int), ("Cout", C.c_int), ("out_pad", C.c_int),
-                ("KS", C.c_int), ("stride", C.c_int), ("pad_top", C.c_int), ("pad_left", C.c_int), ("upsample", C.c_int), ("dtype", C.c_int)]
+                ("KS", C.c_int), ("stride", C.c_int), ("pad_top", C.c_int), ("pad_left", C.c_int), ("upsample", C.c_int), ("dtype", C.c_int),
+                ("chan_bias", C.c_void_p)]
 
 
 class WgradTokProblem(C.Structure):
@@ -123,7 +124,7 @@ class PlanOp(C.Structure):
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_GRAD = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3 = 0, 1
-ABI_VERSION = 12
+ABI_VERSION = 13
 DT_BF16, DT_F16 = 0, 1
 _P, _I, _F, _L, _U64, _U, _D = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_ulonglong, C.c_uint, C.c_double
 
@@ -225,6 +226,9 @@ PROTOTYPES = {
     "eegclip_groupnorm16": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _I, _P, _I, _P, _I, _P],
     "eegclip_softmax_rows16": [_P, _I, _I, _L, _F, _I, _P],
     "eegclip_vae_sample16": [_P, _P, _P, _L, _I, _I, _P],
+    "eegclip_layernorm16": [_P, _L, _P, _P, _P, _L, _I, _I, _F, _I, _P],
+    "eegclip_geglu16": [_P, _P, _I, _I, _I, _P],
+    "eegclip_concat16": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "eegclip_head_gemm_slices": [_I, _I, _I],
     "eegclip_head_gemm": [C.POINTER(HeadGemmDesc), _P],
     "eegclip_head_act": [_P, _I, _L, _P, _P, _P, _P, _P, _I, _I, _P],

@@ -92,12 +92,16 @@ struct cv_args {
     int KS, stride, oy, ox, up;        // source pixel of output (y, x), tap (ky, kx): (y * stride + ky + oy, x * stride + kx + ox), or with `up`
                                        // (((y + ky - 1) >> 1) + 1, ((x + kx - 1) >> 1) + 1) in the padded input frame
     int M, tiles_n, ntiles, chunk;
+    const unsigned short* cb;          // (N, Cout) per-image channel bias, or null (EXT forms only)
 };
 
+// EXT: the UNet's form (csrc/unet.hip's layers around it; diffusers 0.30.0 UNet2DConditionModel) -- Cout % 64 == 0 with the last 128-wide N tile masked (weight
+// rows >= Cout are never read: those DMA lanes fetch row Cout - 1, whose columns nobody stores) and the per-image channel bias `cb` in the epilogue (ResnetBlock2D's
+// time-embedding add, folded into conv1).  EXT = false is the VAE's form, unchanged.
 // SPEC (round 6): four extra PRODUCER waves issue every LDS-DMA instruction (and do the address arithmetic in front of it); the four MFMA waves only read
 // fragments and feed the matrix pipe, and meet the producers at the one barrier per k-tile -- a wave that does both is in order and stalls in every DMA issue
 // with its MFMAs unissued behind it (csrc/infonce_fused.hip, NPRD).
-template <bool F16, bool SPEC>
+template <bool F16, bool SPEC, bool EXT>
 __global__ __launch_bounds__(SPEC ? 512 : 256) void conv16_kernel(const cv_args a) {
     EEG_LDS_BASE(unsigned char, lds);
     const int logical = (int)(blockIdx.x & 7) * a.chunk + (int)(blockIdx.x >> 3);
@@ -124,7 +128,8 @@ __global__ __launch_bounds__(SPEC ? 512 : 256) void conv16_kernel(const cv_args 
         py[i] = rem / a.Wo;
         px[i] = rem - py[i] * a.Wo;
         acol[i] = col;
-        wsrc[i] = a.W + (long long)(n0 + row) * a.KS * a.KS * a.Cin + col;
+        const int wrow = EXT && n0 + row >= a.Cout ? a.Cout - 1 : n0 + row;
+        wsrc[i] = a.W + (long long)wrow * a.KS * a.KS * a.Cin + col;
         // pixel index of tap (0, 0) in the padded input frame (plain form) / of the frame row 0 of this image (`up`: the source row depends on the tap's parity)
         pbase[i] = a.up ? pn[i] * a.Hp : (pn[i] * a.Hp + py[i] * a.stride + a.oy) * a.Wp + px[i] * a.stride + a.ox;
     }
@@ -258,14 +263,17 @@ __global__ __launch_bounds__(SPEC ? 512 : 256) void conv16_kernel(const cv_args 
 #pragma unroll
             for (int eq = 0; eq < 4; ++eq) {
                 const int n = n0 + wn * 64 + 32 * j + 8 * eq + 4 * h;
-                cv_u16x4 bv = cv_u16x4{0, 0, 0, 0}, rv = cv_u16x4{0, 0, 0, 0};
+                if (EXT && n >= a.Cout) continue;
+                cv_u16x4 bv = cv_u16x4{0, 0, 0, 0}, rv = cv_u16x4{0, 0, 0, 0}, cbv = cv_u16x4{0, 0, 0, 0};
                 if (a.bias) bv = *reinterpret_cast<const cv_u16x4*>(a.bias + n);
                 if (a.R) rv = *reinterpret_cast<const cv_u16x4*>(a.R + opix + n);
+                if (EXT && a.cb) cbv = *reinterpret_cast<const cv_u16x4*>(a.cb + (long long)n_ * a.Cout + n);
                 cv_u16x4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float v = acc[j][i][4 * eq + e];
                     if (a.bias) v += cv_to_f32<F16>(bv[e]);
+                    if (EXT && a.cb) v += cv_to_f32<F16>(cbv[e]);
                     if (a.R) v += cv_to_f32<F16>(rv[e]);
                     o[e] = cv_from_f32<F16>(v);
                 }
@@ -374,6 +382,53 @@ __global__ __launch_bounds__(256) void gn_stats16_kernel(const unsigned short* _
         atomicAdd(sums + ((long long)n_ * groups + g) * 2 + 1, (double)red[groups + g]);
     }
 }
+// Statistics for the channel counts the vector form above does not take (the UNet's 320 / 640 / 960 / 1280 / 1920 / 2560 channels in 32 groups: 256 % (C / 8)
+// != 0, or 2 mod 4 channels per group), in a FIXED order so that two passes over one tensor give bit-identical sums: item (pixel lane pl, 8-channel chunk cc),
+// item i = pl * c8n + cc, belongs to thread i % 256 (a thread may own two); the item walks pixels p0 + pl, p0 + pl + ppi, .. and keeps (sum, sum of squares)
+// per channel PAIR (a group has an even channel count: both channels of a pair share it).  The pairs meet per group in LDS in index order; one fp64 atomic
+// pair per (workgroup, group), as in the vector form.  (The per-channel walk it replaces for these counts added float partials into LDS with atomics: no
+// fixed order.)
+template <bool F16>
+__global__ __launch_bounds__(256) void gn_stats16_pairs_kernel(const unsigned short* __restrict__ x, int H, int W, int C, int pad, int groups,
+                                                               double* __restrict__ sums) {
+    EEG_LDS_BASE(float, part);                               // [ppi * c8n][4 pairs][2]
+    const int n_ = blockIdx.y, t = threadIdx.x, hw = H * W, Wp = W + 2 * pad, Hp = H + 2 * pad;
+    const int p0 = blockIdx.x * GN_PB, p1 = p0 + GN_PB < hw ? p0 + GN_PB : hw;
+    const int c8n = C / 8, ppi = c8n < 256 ? 256 / c8n : 1, items = ppi * c8n, ppg = C / groups / 2;
+    for (int i = t; i < items; i += 256) {
+        const int pl = i / c8n, cc = i - pl * c8n;
+        float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int p = p0 + pl; p < p1; p += ppi) {
+            const int y = p / W, xx = p - y * W;
+            const cv_u16x8 v = *reinterpret_cast<const cv_u16x8*>(x + (((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C + 8 * cc);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float a = cv_to_f32<F16>(v[2 * j]), b = cv_to_f32<F16>(v[2 * j + 1]);
+                s[j] += a + b;
+                q[j] += a * a + b * b;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            part[8 * i + 2 * j] = s[j];
+            part[8 * i + 2 * j + 1] = q[j];
+        }
+    }
+    __syncthreads();
+    for (int g = t; g < groups; g += 256) {
+        float s_ = 0.f, q_ = 0.f;
+        for (int l = 0; l < ppi; ++l)
+            for (int k = 0; k < ppg; ++k) {
+                const int pr = g * ppg + k;                  // channel pair index: chunk pr / 4, pair pr % 4 of it
+                const float* e = part + 8 * (l * c8n + (pr >> 2)) + 2 * (pr & 3);
+                s_ += e[0];
+                q_ += e[1];
+            }
+        atomicAdd(sums + ((long long)n_ * groups + g) * 2, (double)s_);
+        atomicAdd(sums + ((long long)n_ * groups + g) * 2 + 1, (double)q_);
+    }
+}
+
 // apply: y = (x - mean) * rstd * gamma + beta (then SiLU if `silu`), written into another frame (its own padding); 4 consecutive channels per thread.  Every workgroup
 // first turns the (image, group) sums into a (mean, 1 / sqrt(var + eps)) table in LDS (the first version redid the fp64 division and square root per 4 channels)
 template <bool F16>
@@ -408,6 +463,43 @@ __global__ __launch_bounds__(256) void gn_apply16_kernel(const unsigned short* _
             o[e] = cv_from_f32<F16>(v);
         }
         *reinterpret_cast<cv_u16x4*>(y + (((long long)n_ * Hop + yy + opad) * Wop + xx + opad) * C + c) = o;
+    }
+}
+
+// apply with 2 consecutive channels per thread (C / groups even but not a multiple of 4: both channels of a pair share a group)
+template <bool F16>
+__global__ __launch_bounds__(256) void gn_apply16_c2_kernel(const unsigned short* __restrict__ x, int N, int H, int W, int C, int pad, int groups,
+                                                             const double* __restrict__ sums, const unsigned short* __restrict__ gamma,
+                                                             const unsigned short* __restrict__ beta, float eps, int silu_on, unsigned short* __restrict__ y, int opad) {
+    EEG_LDS_BASE(float, tab);                                // [N * groups][2]
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    const int c2n = C / 2, hw = H * W, Wp = W + 2 * pad, Hp = H + 2 * pad, Wop = W + 2 * opad, Hop = H + 2 * opad, cpg = C / groups;
+    const long long total = (long long)N * hw * c2n;
+    const double cnt = (double)hw * cpg;
+    for (int i = threadIdx.x; i < N * groups; i += 256) {
+        const double mu = sums[2 * (long long)i] / cnt;
+        double var = sums[2 * (long long)i + 1] / cnt - mu * mu;
+        if (var < 0.0) var = 0.0;
+        tab[2 * i] = (float)mu;
+        tab[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    }
+    __syncthreads();
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
+        const int c = 2 * (int)(q % c2n);
+        const long long pq = q / c2n;
+        const int n_ = (int)(pq / hw), p = (int)(pq - (long long)n_ * hw), yy = p / W, xx = p - yy * W;
+        const int g = c / cpg;
+        const float mean = tab[2 * (n_ * groups + g)], rstd = tab[2 * (n_ * groups + g) + 1];
+        const u16x2 xv = *reinterpret_cast<const u16x2*>(x + (((long long)n_ * Hp + yy + pad) * Wp + xx + pad) * C + c);
+        const u16x2 gv = *reinterpret_cast<const u16x2*>(gamma + c), bv = *reinterpret_cast<const u16x2*>(beta + c);
+        u16x2 o;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            float v = (cv_to_f32<F16>(xv[e]) - mean) * rstd * cv_to_f32<F16>(gv[e]) + cv_to_f32<F16>(bv[e]);
+            if (silu_on) v = silu(v);
+            o[e] = cv_from_f32<F16>(v);
+        }
+        *reinterpret_cast<u16x2*>(y + (((long long)n_ * Hop + yy + opad) * Wop + xx + opad) * C + c) = o;
     }
 }
 
@@ -484,26 +576,34 @@ extern "C" int eegclip_conv16(const eegclip_conv16_desc* d, void* stream) {
     const long long M = (long long)d->N * d->Ho * d->Wo;
     if (M > 0x7fffffffLL) return EEGCLIP_EINVAL;
     a.M = (int)M;
+    a.cb = static_cast<const unsigned short*>(d->chan_bias);
     const bool f16 = d->dtype == EEGCLIP_DT_F16;
-    const bool mfma = d->Cin % CV_K == 0 && d->Cout % CV_T == 0;
-    if (mfma) {
+    const bool mfma = d->Cin % CV_K == 0 && d->Cout % CV_T == 0 && !d->chan_bias;
+    const size_t wbytes = (size_t)d->Cout * d->KS * d->KS * d->Cin * 2;
+    // the UNet's form: Cout % 64 with a channel bias, or with weights beyond what the direct kernel takes (shapes it took before keep it)
+    const bool ext = d->Cin % CV_K == 0 && d->Cout % 64 == 0 && !mfma && (d->chan_bias || wbytes > 150 * 1024);
+    if (mfma || ext) {
         if ((reinterpret_cast<uintptr_t>(d->in) | reinterpret_cast<uintptr_t>(d->W)) & 15u) return EEGCLIP_EALIGN;
-        if ((reinterpret_cast<uintptr_t>(d->out) | reinterpret_cast<uintptr_t>(d->bias) | reinterpret_cast<uintptr_t>(d->residual)) & 7u) return EEGCLIP_EALIGN;
-        a.tiles_n = d->Cout / CV_T;
+        if ((reinterpret_cast<uintptr_t>(d->out) | reinterpret_cast<uintptr_t>(d->bias) | reinterpret_cast<uintptr_t>(d->residual) |
+             reinterpret_cast<uintptr_t>(d->chan_bias)) & 7u) return EEGCLIP_EALIGN;
+        a.tiles_n = (d->Cout + CV_T - 1) / CV_T;
         a.ntiles = a.tiles_n * ((a.M + CV_T - 1) / CV_T);
         a.chunk = (a.ntiles + 7) / 8;
         const size_t lds = (size_t)CV_NS * CV_STAGE_B;
         static const bool spec = [] { const char* e = getenv("EEGCLIP_CONV16_PRODUCERS"); return !(e && e[0] == '0'); }();      // (A/B aid)
-        if (spec) {
-            if (f16) EEG_LAUNCH((conv16_kernel<true, true>), dim3((unsigned)(8 * a.chunk)), dim3(512), lds, stream, a);
-            else     EEG_LAUNCH((conv16_kernel<false, true>), dim3((unsigned)(8 * a.chunk)), dim3(512), lds, stream, a);
+        const dim3 grid((unsigned)(8 * a.chunk)), block(spec ? 512 : 256);
+#define EEG_CV(F, S, X) EEG_LAUNCH((conv16_kernel<F, S, X>), grid, block, lds, stream, a)
+        if (ext) {
+            if (spec) { if (f16) EEG_CV(true, true, true); else EEG_CV(false, true, true); }
+            else      { if (f16) EEG_CV(true, false, true); else EEG_CV(false, false, true); }
         } else {
-            if (f16) EEG_LAUNCH((conv16_kernel<true, false>), dim3((unsigned)(8 * a.chunk)), dim3(256), lds, stream, a);
-            else     EEG_LAUNCH((conv16_kernel<false, false>), dim3((unsigned)(8 * a.chunk)), dim3(256), lds, stream, a);
+            if (spec) { if (f16) EEG_CV(true, true, false); else EEG_CV(false, true, false); }
+            else      { if (f16) EEG_CV(true, false, false); else EEG_CV(false, false, false); }
         }
+#undef EEG_CV
         return (int)hipGetLastError();
     }
-    const size_t wbytes = (size_t)d->Cout * d->KS * d->KS * d->Cin * 2;
+    if (d->chan_bias) return EEGCLIP_EINVAL;                 // (the channel bias is an epilogue of the matrix-core forms only)
     if (wbytes > 150 * 1024) return EEGCLIP_EINVAL;           // (the small-channel layers of the VAE: at most 512 -> 8, 72 KB)
     a.tiles_n = a.ntiles = a.chunk = 0;
     long long g = (M * d->Cout + 255) / 256;
@@ -515,20 +615,44 @@ extern "C" int eegclip_conv16(const eegclip_conv16_desc* d, void* stream) {
 
 extern "C" int eegclip_groupnorm16(const void* x, int N, int H, int W, int C, int pad, int groups, const void* gamma, const void* beta, float eps, int silu_on,
                                    void* y, int out_pad, double* sums, int dtype, void* stream) {
-    if (!x || !gamma || !beta || !y || !sums || N < 1 || H < 1 || W < 1 || C < 4 || groups < 1 || C % groups || (C / groups) % 4 || pad < 0 || pad > 1 ||
+    if (!x || !gamma || !beta || !y || !sums || N < 1 || H < 1 || W < 1 || C < 4 || groups < 1 || C % groups || (C / groups) % 2 || pad < 0 || pad > 1 ||
         out_pad < 0 || out_pad > 1 || (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16))
         return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) | reinterpret_cast<uintptr_t>(y) |
          reinterpret_cast<uintptr_t>(sums)) & 7u)
         return EEGCLIP_EALIGN;
     const bool f16 = dtype == EEGCLIP_DT_F16;
+    const int cpg = C / groups, c8n = C / 8;
+    const bool a16 = (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
+    // statistics: the vector form (the VAE's channel counts; the condition gn_stats16_kernel takes it under) keeps its kernel; other counts with C % 8 == 0
+    // and a 16-byte aligned x take the fixed-order pair form; the per-channel walk stays for the rest (4 k channels per group only)
+    const bool vec = cpg % 4 == 0 && (C & 7) == 0 && c8n <= 256 && 256 % c8n == 0 && (groups & 1) == 0 && groups <= 256 && a16;
+    const bool pairs = !vec && (C & 7) == 0 && a16 && c8n <= 2048;
+    if (!vec && !pairs && cpg % 4) return EEGCLIP_EINVAL;
     if ((long long)N * groups > 4096) return EEGCLIP_EINVAL;     // (the apply kernel keeps the (mean, rstd) table of every (image, group) in LDS)
     hipError_t e = hipMemsetAsync(sums, 0, (size_t)N * groups * 2 * sizeof(double), (hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
     const dim3 gs((unsigned)((H * W + GN_PB - 1) / GN_PB), (unsigned)N);
-    const size_t lds = (2 * (size_t)groups + 256 * 4) * sizeof(float);
-    if (f16) EEG_LAUNCH((gn_stats16_kernel<true>), gs, dim3(256), lds, stream, static_cast<const unsigned short*>(x), H, W, C, pad, groups, sums);
-    else     EEG_LAUNCH((gn_stats16_kernel<false>), gs, dim3(256), lds, stream, static_cast<const unsigned short*>(x), H, W, C, pad, groups, sums);
+    if (pairs) {
+        const size_t lds_p = (size_t)(c8n < 256 ? 256 / c8n : 1) * c8n * 8 * sizeof(float);
+        if (f16) EEG_LAUNCH((gn_stats16_pairs_kernel<true>), gs, dim3(256), lds_p, stream, static_cast<const unsigned short*>(x), H, W, C, pad, groups, sums);
+        else     EEG_LAUNCH((gn_stats16_pairs_kernel<false>), gs, dim3(256), lds_p, stream, static_cast<const unsigned short*>(x), H, W, C, pad, groups, sums);
+    } else {
+        const size_t lds = (2 * (size_t)groups + 256 * 4) * sizeof(float);
+        if (f16) EEG_LAUNCH((gn_stats16_kernel<true>), gs, dim3(256), lds, stream, static_cast<const unsigned short*>(x), H, W, C, pad, groups, sums);
+        else     EEG_LAUNCH((gn_stats16_kernel<false>), gs, dim3(256), lds, stream, static_cast<const unsigned short*>(x), H, W, C, pad, groups, sums);
+    }
+    if (cpg % 4) {                                           // (2 mod 4 channels per group: the UNet's 320 / 960 channels)
+        long long g2 = ((long long)N * H * W * (C / 2) + 255) / 256;
+        if (g2 > 16384) g2 = 16384;
+#define EEG_GNA2(F)                                                                                                                                       \
+    EEG_LAUNCH((gn_apply16_c2_kernel<F>), dim3((unsigned)g2), dim3(256), (size_t)N * groups * 2 * sizeof(float), stream, static_cast<const unsigned short*>(x), N, H, W, C, pad, \
+               groups, sums, static_cast<const unsigned short*>(gamma), static_cast<const unsigned short*>(beta), eps, silu_on, static_cast<unsigned short*>(y), out_pad)
+        if (f16) EEG_GNA2(true);
+        else     EEG_GNA2(false);
+#undef EEG_GNA2
+        return (int)hipGetLastError();
+    }
     long long g = ((long long)N * H * W * (C / 4) + 255) / 256;
     if (g > 16384) g = 16384;
 #define EEG_GNA(F)                                                                                                                                        \

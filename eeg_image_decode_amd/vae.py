@@ -95,35 +95,13 @@ class _Decoder(nn.Module):
         self.conv_out = nn.Conv2d(rev[-1], 3, 3, padding=1)
 
 
-class SDXLShapedVAE(nn.Module):
-    def __init__(self, block_out_channels=(128, 256, 512, 512), layers_per_block=2, latent_channels=4, scaling_factor=0.13025, dtype=torch.bfloat16,
-                 seed=0):
-        super().__init__()
-        with torch.random.fork_rng(devices=[]):
-            torch.manual_seed(seed)
-            self.encoder = _Encoder(block_out_channels, layers_per_block, latent_channels)
-            self.decoder = _Decoder(block_out_channels, layers_per_block, latent_channels)
-            self.quant_conv = nn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
-            self.post_quant_conv = nn.Conv2d(latent_channels, latent_channels, 1)
-        self.latent_channels, self.scaling_factor = latent_channels, scaling_factor
-        self.downscale = 2 ** (len(block_out_channels) - 1)
-        self.to(dtype)
-        for p in self.parameters():
-            p.requires_grad_(False)
+class _FrameOps(nn.Module):
+    """The padded-frame plumbing shared by SDXLShapedVAE and sdxl_unet.SDXLUNet: convolution weights packed once per parameter version, a pool of padded
+    NHWC frames (borders zero, never written), and the conv16 / groupnorm16 launches over them.  Subclasses call _init_frames() and define .dtype / .device."""
+
+    def _init_frames(self):
         self._packed, self._pool, self._sums = {}, {}, None
 
-    def forward(self, *a, **k):
-        raise EegclipError("SDXLShapedVAE holds parameters; call .encode(image) / .decode(latents) (HIP kernels). There is no eager path.")
-
-    @property
-    def dtype(self):
-        return self.post_quant_conv.weight.dtype
-
-    @property
-    def device(self):
-        return self.post_quant_conv.weight.device
-
-    # ---- plumbing: packed weights, padded frames ---------------------------------------------------------------------------------------------------
     def _w(self, mod):
         """the layer's weight as [Cout][KS * KS][Cin] (what csrc/vae.hip contracts over), packed once per parameter version"""
         w = mod.weight
@@ -149,9 +127,9 @@ class SDXLShapedVAE(nn.Module):
         for f in frames:
             self._pool.setdefault((tuple(f.shape), f._eegclip_pad), []).append(f)
 
-    def _conv(self, x, xpad, mod, out_pad=1, stride=1, pads=None, upsample=False, residual=None, KS=None):
+    def _conv(self, x, xpad, mod, out_pad=1, stride=1, pads=None, upsample=False, residual=None, KS=None, chan_bias=None):
         """x: (N, Hi + 2 xpad, Wi + 2 xpad, Cin) frame -> (N, Ho + 2 out_pad, Wo + 2 out_pad, Cout) frame.  pads = (top, left, bottom, right) zero padding of
-        the convolution (default: "same"); upsample: over the nearest-2x upsampled input"""
+        the convolution (default: "same"); upsample: over the nearest-2x upsampled input; chan_bias: (N, Cout) added per image and channel"""
         N, Hi, Wi, Cin = x.shape[0], x.shape[1] - 2 * xpad, x.shape[2] - 2 * xpad, x.shape[3]
         w = self._w(mod)
         Cout, KS = w.shape[0], (KS or int(round(math.sqrt(w.shape[1]))))
@@ -163,18 +141,56 @@ class SDXLShapedVAE(nn.Module):
         out = self._frame(N, Ho, Wo, Cout, out_pad)
         d = _abi.Conv16Desc(in_=x.data_ptr(), W=w.data_ptr(), out=out.data_ptr(), bias=mod.bias.data_ptr() if mod.bias is not None else None,
                             residual=residual.data_ptr() if residual is not None else None, N=N, Hi=Hi, Wi=Wi, Cin=Cin, in_pad=xpad, Ho=Ho, Wo=Wo, Cout=Cout,
-                            out_pad=out_pad, KS=KS, stride=stride, pad_top=pt, pad_left=pleft, upsample=int(upsample), dtype=_dt(self.dtype))
+                            out_pad=out_pad, KS=KS, stride=stride, pad_top=pt, pad_left=pleft, upsample=int(upsample), dtype=_dt(self.dtype),
+                            chan_bias=chan_bias.data_ptr() if chan_bias is not None else None)
         check(lib().eegclip_conv16(d, raw_stream()), "conv16")
         return out
 
     def _gn(self, x, xpad, mod, silu=True, out_pad=1):
         N, H, W, C = x.shape[0], x.shape[1] - 2 * xpad, x.shape[2] - 2 * xpad, x.shape[3]
-        if self._sums is None or self._sums.numel() < N * GROUPS * 2:
-            self._sums = torch.empty(N * GROUPS * 2, dtype=torch.float64, device=self.device)
+        G = mod.num_groups
+        if self._sums is None or self._sums.numel() < N * G * 2:
+            self._sums = torch.empty(N * G * 2, dtype=torch.float64, device=self.device)
         y = self._frame(N, H, W, C, out_pad)
-        check(lib().eegclip_groupnorm16(x.data_ptr(), N, H, W, C, xpad, GROUPS, mod.weight.data_ptr(), mod.bias.data_ptr(), float(mod.eps), int(silu),
+        check(lib().eegclip_groupnorm16(x.data_ptr(), N, H, W, C, xpad, G, mod.weight.data_ptr(), mod.bias.data_ptr(), float(mod.eps), int(silu),
                                         y.data_ptr(), out_pad, self._sums.data_ptr(), _dt(self.dtype), raw_stream()), "groupnorm16")
         return y
+
+    def _to_frame(self, t):
+        """(N, C, H, W) -> padded NHWC frame (a layout change at the boundary; torch plumbing)"""
+        N, C, H, W = t.shape
+        f = self._frame(N, H, W, C, 1)
+        f[:, 1:-1, 1:-1, :] = t.permute(0, 2, 3, 1)
+        return f
+
+
+class SDXLShapedVAE(_FrameOps):
+    def __init__(self, block_out_channels=(128, 256, 512, 512), layers_per_block=2, latent_channels=4, scaling_factor=0.13025, dtype=torch.bfloat16,
+                 seed=0):
+        super().__init__()
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            self.encoder = _Encoder(block_out_channels, layers_per_block, latent_channels)
+            self.decoder = _Decoder(block_out_channels, layers_per_block, latent_channels)
+            self.quant_conv = nn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
+            self.post_quant_conv = nn.Conv2d(latent_channels, latent_channels, 1)
+        self.latent_channels, self.scaling_factor = latent_channels, scaling_factor
+        self.downscale = 2 ** (len(block_out_channels) - 1)
+        self.to(dtype)
+        for p in self.parameters():
+            p.requires_grad_(False)
+        self._init_frames()
+
+    def forward(self, *a, **k):
+        raise EegclipError("SDXLShapedVAE holds parameters; call .encode(image) / .decode(latents) (HIP kernels). There is no eager path.")
+
+    @property
+    def dtype(self):
+        return self.post_quant_conv.weight.dtype
+
+    @property
+    def device(self):
+        return self.post_quant_conv.weight.device
 
     # ---- blocks (diffusers ResnetBlock2D / Attention / UNetMidBlock2D with one attention, as AutoencoderKL configures them) -------------------------
     def _resnet(self, x, r):
@@ -223,13 +239,6 @@ class SDXLShapedVAE(nn.Module):
         h = self._resnet(h2, m.resnets[1])
         self._done(h2)
         return h
-
-    def _to_frame(self, t):
-        """(N, C, H, W) -> padded NHWC frame (a layout change at the boundary; torch plumbing)"""
-        N, C, H, W = t.shape
-        f = self._frame(N, H, W, C, 1)
-        f[:, 1:-1, 1:-1, :] = t.permute(0, 2, 3, 1)
-        return f
 
     # ---- the two calls of the reference -----------------------------------------------------------------------------------------------------------
     @torch.no_grad()

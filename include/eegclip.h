@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 12
+#define EEGCLIP_ABI_VERSION 13
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -610,9 +610,14 @@ int eegclip_infonce_small_grad(int n, int T, const float* scale, const float* wo
  *                        taps must stay inside the padded frame: stride 2 with pad (0, 1, 0, 1) is the encoder's downsampler).  upsample = 1: `in` is (Hi, Wi)
  *                        and the convolution runs over its nearest-2x upsampling (Ho = 2 Hi; KS 3, stride 1, pad 1) -- Upsample2D + conv without the
  *                        upsampled tensor.  Cin % 64 == 0 and Cout % 128 == 0: implicit GEMM on v_mfma_f32_32x32x16 (the tile loop of eegclip_gemm16, row
- *                        addresses recomputed per tap); otherwise a direct kernel for the 3 / 4 / 8-channel layers (weights <= 150 KB).
+ *                        addresses recomputed per tap); Cin % 64 == 0 and Cout % 64 == 0 with weights > 150 KB or a chan_bias (the UNet's 320-channel
+ *                        layers): the same tile loop with the last 128-wide N tile masked (weight rows >= Cout are not read, their columns are not
+ *                        stored); otherwise a direct kernel for the 3 / 4 / 8-channel layers (weights <= 150 KB; the shapes it took before ABI 13 keep it).  chan_bias (ABI 13): + chan_bias[n][co] in the epilogue of the
+ *                        matrix-core forms (ResnetBlock2D's time-embedding add folded into conv1; diffusers 0.30.0 resnet.py).
  *   eegclip_groupnorm16  y = GroupNorm(x) (* SiLU if silu): statistics over the interior pixels, fp64 sums in `sums` (N * groups * 2 doubles, cleared by the
- *                        call); C / groups a multiple of 4
+ *                        call); C / groups a multiple of 4, or of 2 (the UNet's 320 / 960-channel GroupNorm(32): 10 / 30 channels per group, C % 8 == 0
+ *                        and x 16-byte aligned).  Bit-reproducible for C % 8 == 0 and a 16-byte aligned x: the channel counts of the VAE keep their vector
+ *                        form; since ABI 13 the others (e.g. 320 .. 2560 channels in 32 groups) take a fixed-order form instead of a per-channel walk
  *   eegclip_softmax_rows16   rows of a 16-bit matrix <- softmax(scale * row), in place (the mid-block attention's score matrix)
  *   eegclip_vae_sample16     z = mean + exp(0.5 clamp(logvar, -30, 20)) * noise from moments (pixels, 2 L) = [mean | logvar] (noise NULL: the mode) */
 typedef struct {
@@ -624,12 +629,24 @@ typedef struct {
     int N, Hi, Wi, Cin, in_pad;
     int Ho, Wo, Cout, out_pad;
     int KS, stride, pad_top, pad_left, upsample, dtype;
+    const void* chan_bias;       /* (N, Cout) 16-bit, added per image and channel (the UNet's time embedding), or NULL  (ABI 13) */
 } eegclip_conv16_desc;
 int eegclip_conv16(const eegclip_conv16_desc* d, void* stream);
 int eegclip_groupnorm16(const void* x, int N, int H, int W, int C, int pad, int groups, const void* gamma, const void* beta, float eps, int silu, void* y,
                         int out_pad, double* sums, int dtype, void* stream);
 int eegclip_softmax_rows16(void* s, int rows, int cols, long long ld, float scale, int dtype, void* stream);
 int eegclip_vae_sample16(const void* moments, const void* noise, void* z, long long pixels, int latent_channels, int dtype, void* stream);
+
+/* ---- the SDXL UNet's remaining layers (csrc/unet.hip; Generation/custom_pipeline.py:456-492 loads UNet2DConditionModel from stabilityai/sdxl-turbo, diffusers
+ * 0.30.0 attention.py BasicTransformerBlock / GEGLU, unet_2d_blocks.py skip concatenation), 16-bit in and out, fp32 arithmetic:
+ *   eegclip_layernorm16   y[r] = LayerNorm(x[r]) * gamma + beta over rows of C (C % 8 == 0, C <= 4096; row strides ldx / ldy, multiples of 8), fp32 statistics
+ *   eegclip_geglu16       y[m][j] = x[m][j] * gelu_erf(x[m][D + j]) for x (M, 2 D) -> y (M, D), D % 8 == 0 (the feed-forward's GEGLU, value half first)
+ *   eegclip_concat16      out = cat([a, b], channel) of two padded NHWC frames (N, H + 2 pad, W + 2 pad, Ca | Cb) -> (.., Ca + Cb), interior pixels only (the
+ *                         frame border of `out` is not written); Ca, Cb multiples of 8 */
+int eegclip_layernorm16(const void* x, long long ldx, const void* gamma, const void* beta, void* y, long long ldy, int rows, int C, float eps, int dtype,
+                        void* stream);
+int eegclip_geglu16(const void* x, void* y, int M, int D, int dtype, void* stream);
+int eegclip_concat16(const void* a, const void* b, void* out, int N, int H, int W, int pad, int Ca, int Cb, int out_pad, int dtype, void* stream);
 
 /* ---- the projection head's GEMMs at M = the batch (csrc/head_gemm.hip; Retrieval/ATMS_retrieval.py:157-167 forward, its input gradients, and the query
  * gradient of the loss, models/loss.py:122-140): C[m][n] = sum_k A[m][k] B[n][k] from k-contiguous bf16 hi | lo planes like eegclip_gemm_planes, but
