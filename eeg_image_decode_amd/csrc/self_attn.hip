@@ -18,6 +18,11 @@
 // s - m is exact near the maximum and never positive.
 // probabilities rounded to the I/O dtype before P V; O accumulated in fp32, divided by the fp32 row sum once and rounded once.
 // Tail keys are zero-filled in LDS and masked to -inf; tail query rows are clamped on load and never stored.
+// CAUSAL (CLIP's text encoders, csrc/clip_text.hip; Tq == Tk): key j reaches query i only if j <= i.  Scores of later keys are set to -inf where the
+// tail mask is applied, in the tiles that cross the workgroup's diagonal only, and the key loop ends with the tile that holds the workgroup's last
+// query.  Key 0 is visible to every query, so the running maximum is still finite from the first tile on; a tile that is wholly masked for one
+// query (the second tile of a 128-query workgroup, for its first 64 queries) leaves that query's m, l and accumulators as they were
+// (exp2(-inf) = 0, alpha = exp2(0) = 1).  The non-causal instantiations compile to the code they had without the flag.
 #include "attn16.h"
 
 namespace eeg {
@@ -85,7 +90,7 @@ __device__ __forceinline__ void sa_commit(const sa_stage& r, unsigned short* Ks,
     }
 }
 
-template <bool F16, int QT>
+template <bool F16, int QT, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
     EEG_LDS_BASE(unsigned short, lds);      // [2][K tile | V tile]
     const int b = blockIdx.z, h = blockIdx.y;
@@ -93,7 +98,11 @@ __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
     const int fr = lane & 15, g = lane >> 4;
     const unsigned short* kb = a.k + (long long)b * a.Tk * a.ldk + h * SA_D;
     const unsigned short* vb = a.v + (long long)b * a.Tk * a.ldv + h * SA_D;
-    const int nkt = (a.Tk + SA_KT - 1) / SA_KT;
+    int nkt = (a.Tk + SA_KT - 1) / SA_KT;
+    if (CAUSAL) {                                                          // stop after the tile of the workgroup's last query (Tq == Tk)
+        const int qend = (int)(blockIdx.x + 1) * (64 * QT), qlast = (qend < a.Tq ? qend : a.Tq) - 1;
+        if (qlast / SA_KT + 1 < nkt) nkt = qlast / SA_KT + 1;
+    }
 
     sa_stage st;
     sa_issue(st, a, kb, vb, 0);
@@ -140,6 +149,16 @@ __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
 #pragma unroll
                     for (int p = 0; p < QT; ++p) s[p][t][r] = in ? s[p][t][r] : -INFINITY;
                 }
+        }
+        if (CAUSAL && kt * SA_KT + SA_KT - 1 > (int)blockIdx.x * (64 * QT)) {   // the tile reaches past the workgroup's first query: keys > query -> -inf
+#pragma unroll
+            for (int p = 0; p < QT; ++p) {
+                const int qrow = blockIdx.x * (64 * QT) + (p * 4 + wave) * 16 + fr;
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) s[p][t][r] = kt * SA_KT + 16 * t + 4 * g + r <= qrow ? s[p][t][r] : -INFINITY;
+            }
         }
         bf16x8 pa[QT][2];
 #pragma unroll
@@ -219,11 +238,12 @@ extern "C" int eegclip_self_attn_supported(int head_dim, long long ldq, long lon
     return 0;
 }
 
-extern "C" int eegclip_self_attn_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo,
-                                     int B, int Tq, int Tk, int heads, int head_dim, float scale, int dtype, void* stream) {
+static int sa_forward(bool causal, const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B, int Tq,
+                      int Tk, int heads, int head_dim, float scale, int dtype, void* stream) {
     const int rc = eegclip_self_attn_supported(head_dim, ldq, ldk, ldv, ldo);
     if (rc) return rc;
     if (!q || !k || !v || !out || B < 1 || Tq < 1 || Tk < 1 || heads < 1 || B > 65535 || heads > 65535 || !(scale > 0.f) || !(scale < INFINITY)) return EEGCLIP_EINVAL;
+    if (causal && Tq != Tk) return EEGCLIP_EINVAL;
     if (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16) return EEGCLIP_EINVAL;
     const long long C = (long long)heads * SA_D;
     if (ldq < C || ldk < C || ldv < C || ldo < C) return EEGCLIP_EINVAL;
@@ -237,12 +257,32 @@ extern "C" int eegclip_self_attn_fwd(const void* q, long long ldq, const void* k
     const bool f16 = dtype == EEGCLIP_DT_F16;
     if (wg128 >= 512) {
         const dim3 grid((Tq + 127) / 128, heads, B);
-        if (f16) EEG_LAUNCH((self_attn_kernel<true, 2>), grid, dim3(256), lds, stream, a);
-        else     EEG_LAUNCH((self_attn_kernel<false, 2>), grid, dim3(256), lds, stream, a);
+        if (causal) {
+            if (f16) EEG_LAUNCH((self_attn_kernel<true, 2, true>), grid, dim3(256), lds, stream, a);
+            else     EEG_LAUNCH((self_attn_kernel<false, 2, true>), grid, dim3(256), lds, stream, a);
+        } else {
+            if (f16) EEG_LAUNCH((self_attn_kernel<true, 2>), grid, dim3(256), lds, stream, a);
+            else     EEG_LAUNCH((self_attn_kernel<false, 2>), grid, dim3(256), lds, stream, a);
+        }
     } else {
         const dim3 grid((Tq + 63) / 64, heads, B);
-        if (f16) EEG_LAUNCH((self_attn_kernel<true, 1>), grid, dim3(256), lds, stream, a);
-        else     EEG_LAUNCH((self_attn_kernel<false, 1>), grid, dim3(256), lds, stream, a);
+        if (causal) {
+            if (f16) EEG_LAUNCH((self_attn_kernel<true, 1, true>), grid, dim3(256), lds, stream, a);
+            else     EEG_LAUNCH((self_attn_kernel<false, 1, true>), grid, dim3(256), lds, stream, a);
+        } else {
+            if (f16) EEG_LAUNCH((self_attn_kernel<true, 1>), grid, dim3(256), lds, stream, a);
+            else     EEG_LAUNCH((self_attn_kernel<false, 1>), grid, dim3(256), lds, stream, a);
+        }
     }
     return (int)hipGetLastError();
+}
+
+extern "C" int eegclip_self_attn_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo,
+                                     int B, int Tq, int Tk, int heads, int head_dim, float scale, int dtype, void* stream) {
+    return sa_forward(false, q, ldq, k, ldk, v, ldv, out, ldo, B, Tq, Tk, heads, head_dim, scale, dtype, stream);
+}
+
+extern "C" int eegclip_self_attn_causal_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo,
+                                            int B, int Tq, int Tk, int heads, int head_dim, float scale, int dtype, void* stream) {
+    return sa_forward(true, q, ldq, k, ldk, v, ldv, out, ldo, B, Tq, Tk, heads, head_dim, scale, dtype, stream);
 }

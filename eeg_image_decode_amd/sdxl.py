@@ -24,6 +24,7 @@ self-contained:
                                                      the loop, the schedulers and the attention kernels run and are measured end to end.
 * StandInSDXLPipeline / Generator4Embeds             the wrapper (custom_pipeline.py:456-492).  With diffusers + checkpoints it drives the real
                                                      pipeline; offline it drives the stand-in and returns LATENTS (there is no VAE to decode).
+                                                     text_encoder= / text_encoder_2= (clip_text.py): encode_prompt as diffusers' SDXL pipeline does it.
 """
 import math
 
@@ -226,10 +227,10 @@ def _row_layout(t, name):
     return t, ld
 
 
-def self_attention(q, k, v, heads, scale=None, out=None):
+def self_attention(q, k, v, heads, scale=None, out=None, causal=False):
     """softmax(scale * q k^T) v per head of 64 (flash-style, csrc/self_attn.hip: no T x T buffer).  q (B, Tq, C), k / v (B, Tk, C), C = heads * 64,
     fp16 or bf16; the three may be column slices of one fused (B, T, 3C) projection (consumed in place).  scale defaults to 1/8 (diffusers'
-    attn.scale).  Returns `out` (B, Tq, C), which may be given."""
+    attn.scale).  causal: key j reaches query i only if j <= i (CLIP's text encoders; Tq == Tk).  Returns `out` (B, Tq, C), which may be given."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         require_cuda(t, n)
     if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
@@ -244,6 +245,8 @@ def self_attention(q, k, v, heads, scale=None, out=None):
         raise EegclipError(f"self_attention: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
     if B * Tq * Tk == 0:
         raise EegclipError("self_attention: empty input")
+    if causal and Tq != Tk:
+        raise EegclipError(f"self_attention: the causal form takes Tq == Tk (got {Tq}, {Tk})")
     q, ldq = _row_layout(q, "q")
     k, ldk = _row_layout(k, "k")
     v, ldv = _row_layout(v, "v")
@@ -253,8 +256,9 @@ def self_attention(q, k, v, heads, scale=None, out=None):
         raise EegclipError(f"self_attention: out {tuple(out.shape)} {out.dtype} does not match ({B}, {Tq}, {C}) {q.dtype}")
     out, ldo = _row_layout(out, "out")
     scale = 1.0 / math.sqrt(64) if scale is None else float(scale)
-    check(lib().eegclip_self_attn_fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, B, Tq, Tk, heads, 64, scale,
-                                      _dt(q), _stream()), "self_attn_fwd")
+    fwd = lib().eegclip_self_attn_causal_fwd if causal else lib().eegclip_self_attn_fwd
+    check(fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, B, Tq, Tk, heads, 64, scale, _dt(q), _stream()),
+          "self_attn_causal_fwd" if causal else "self_attn_fwd")
     return out
 
 
@@ -649,13 +653,17 @@ class _Output:
 
 
 class StandInSDXLPipeline:
-    """What `generate_ip_adapter_embeds` needs from a diffusers StableDiffusionXLPipeline, around the stand-in UNet: scheduler, empty-prompt
-    embeddings (there is no text encoder offline: prompt '' maps to fixed embeddings, like the reference's constant empty prompt), micro-conditioning
-    ids.  vae: a vae.SDXLShapedVAE (round 6: SDXL's VAE layout on csrc/vae.hip) -- `low_level_image` is then encoded by it
+    """What `generate_ip_adapter_embeds` needs from a diffusers StableDiffusionXLPipeline, around the stand-in UNet: scheduler, prompt embeddings,
+    micro-conditioning ids.  text_encoder / text_encoder_2: clip_text.CLIPTextEncoder pair (sdxl_text_encoder(), sdxl_text_encoder_2()); encode_prompt
+    then does what StableDiffusionXLPipeline.encode_prompt does.  tokenizer / tokenizer_2: clip_text.BPETokenizer pair (tokenizer_2 with pad_token "!");
+    without them only the empty prompt (and prompt_ids=) can be encoded.  With no encoder at all, prompt '' maps to fixed random embeddings, like the
+    reference's constant empty prompt, and any other prompt raises.
+    vae: a vae.SDXLShapedVAE (round 6: SDXL's VAE layout on csrc/vae.hip) -- `low_level_image` is then encoded by it
     (custom_pipeline_low_level.py:8-31) and output_type "pt" / "np" decodes the final latents (custom_pipeline.py:421 + image_processor.postprocess:
     image / 2 + 0.5 clamped to [0, 1]); without one, output_type must be "latent" unless `vae_decode` / `vae_encode` callables are supplied."""
 
-    def __init__(self, unet=None, scheduler=None, device="cuda", dtype=torch.float16, default_sample_size=64, vae_decode=None, vae_encode=None, vae=None):
+    def __init__(self, unet=None, scheduler=None, device="cuda", dtype=torch.float16, default_sample_size=64, vae_decode=None, vae_encode=None, vae=None,
+                 text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None):
         self.unet = (unet if unet is not None else SDXLShapedUNet(dtype=dtype)).to(device)
         self.scheduler = scheduler if scheduler is not None else EulerAncestralDiscreteScheduler()
         self.device, self.dtype = device, dtype
@@ -672,17 +680,82 @@ class StandInSDXLPipeline:
         self.empty_prompt_embeds = (torch.randn(1, 77, 2048, generator=g) * 0.5).to(device=device, dtype=dtype)
         self.empty_pooled_embeds = (torch.randn(1, 1280, generator=g) * 0.5).to(device=device, dtype=dtype)
         self.text_encoder_projection_dim = 1280
+        if (text_encoder is None) != (text_encoder_2 is None):
+            raise EegclipError("StandInSDXLPipeline takes both text encoders or neither (SDXL concatenates their hidden states)")
+        self.text_encoder = text_encoder.to(device) if text_encoder is not None else None
+        self.text_encoder_2 = text_encoder_2.to(device) if text_encoder_2 is not None else None
+        self.tokenizer, self.tokenizer_2 = tokenizer, tokenizer_2
+        if text_encoder_2 is not None:
+            if text_encoder_2.config.projection_dim is None:
+                raise EegclipError("text_encoder_2 must have a text_projection (its out[0] is the pooled text_embeds of the micro-conditioning)")
+            self.text_encoder_projection_dim = text_encoder_2.config.projection_dim
+
+    def _prompt_ids(self, which, prompts):
+        """(B, 77) ids of tokenizer `which` (0 / 1) for a list of prompts; '' needs no tokenizer (clip_text.empty_prompt_ids)"""
+        from .clip_text import EOS_ID, empty_prompt_ids
+        tok = (self.tokenizer, self.tokenizer_2)[which]
+        if tok is not None:
+            return tok(prompts)
+        if any(p != "" for p in prompts):
+            raise EegclipError("encoding a prompt other than '' needs CLIP's tokenizers: pass tokenizer= / tokenizer_2= built from the checkpoint's "
+                               "tokenizer/vocab.json + tokenizer/merges.txt and tokenizer_2/vocab.json + tokenizer_2/merges.txt "
+                               "(clip_text.BPETokenizer; tokenizer_2 with pad_token='!'), or pass prompt_ids=(ids_1, ids_2)")
+        return [empty_prompt_ids(EOS_ID if which == 0 else 0) for _ in prompts]      # tokenizer pads with <|endoftext|>, tokenizer_2 with "!" = 0
+
+    def _encode_text(self, prompt, prompt_2, batch_size, clip_skip, prompt_ids=None):
+        """StableDiffusionXLPipeline.encode_prompt (diffusers 0.30.0) for one polarity: per (tokenizer, encoder) pair hidden_states[-2]
+        (-(clip_skip + 2) with clip_skip), concatenated on the feature axis; pooled = out[0] of the SECOND encoder.  The first encoder stops at the
+        layer whose output is read."""
+        if prompt_ids is not None:
+            ids = list(prompt_ids)
+            if len(ids) != 2:
+                raise EegclipError("prompt_ids takes (ids of tokenizer, ids of tokenizer_2)")
+        else:
+            p1 = [prompt] if isinstance(prompt, str) else list(prompt)
+            prompt_2 = prompt if prompt_2 is None else prompt_2
+            p2 = [prompt_2] if isinstance(prompt_2, str) else list(prompt_2)
+            if len(p1) == 1 and batch_size > 1:                               # (several image embeddings with the one prompt)
+                p1 = p1 * batch_size
+            if len(p2) == 1 and len(p1) > 1:
+                p2 = p2 * len(p1)
+            if len(p1) != len(p2):
+                raise EegclipError(f"prompt has {len(p1)} entries, prompt_2 {len(p2)}")
+            ids = [self._prompt_ids(0, p1), self._prompt_ids(1, p2)]
+        skip = 0 if clip_skip is None else int(clip_skip)
+        enc1, enc2 = self.text_encoder, self.text_encoder_2
+        n1 = enc1.config.num_hidden_layers - 1 - skip
+        if n1 < 0 or enc2.config.num_hidden_layers - 1 - skip < 0:
+            raise EegclipError(f"clip_skip = {clip_skip} reaches before the embeddings of a text encoder")
+        h1 = enc1(ids[0], output_hidden_states=True, num_layers=n1).hidden_states[-1]
+        out2 = enc2(ids[1], output_hidden_states=True)
+        h2 = out2.hidden_states[-(skip + 2)]
+        if h1.shape[:2] != h2.shape[:2]:
+            raise EegclipError(f"the two tokenizations differ in shape: {tuple(h1.shape[:2])} and {tuple(h2.shape[:2])}")
+        return torch.cat([h1.to(self.dtype), h2.to(self.dtype)], dim=-1), out2[0].to(self.dtype)
 
     def encode_prompt(self, prompt, batch_size, prompt_embeds=None, pooled_prompt_embeds=None, negative_prompt_embeds=None,
-                      negative_pooled_prompt_embeds=None, do_classifier_free_guidance=False):
+                      negative_pooled_prompt_embeds=None, do_classifier_free_guidance=False, prompt_2=None, negative_prompt=None, negative_prompt_2=None,
+                      clip_skip=None, prompt_ids=None, negative_prompt_ids=None):
         if prompt_embeds is None:
-            if prompt not in (None, "", [""] * batch_size):
-                raise EegclipError("no text encoder in the offline build: pass prompt_embeds / pooled_prompt_embeds, or the empty prompt the reference uses")
-            prompt_embeds = self.empty_prompt_embeds.expand(batch_size, -1, -1)
-            pooled_prompt_embeds = self.empty_pooled_embeds.expand(batch_size, -1)
-        if do_classifier_free_guidance and negative_prompt_embeds is None:       # (an empty negative prompt embeds to zeros under force_zeros_for_empty_prompt)
-            negative_prompt_embeds = torch.zeros_like(prompt_embeds)
-            negative_pooled_prompt_embeds = torch.zeros_like(pooled_prompt_embeds)
+            if self.text_encoder is not None:
+                prompt_embeds, pooled_prompt_embeds = self._encode_text("" if prompt is None else prompt, prompt_2, batch_size, clip_skip, prompt_ids)
+                if prompt_embeds.shape[0] != batch_size:
+                    raise EegclipError(f"{prompt_embeds.shape[0]} prompts for a batch of {batch_size}")
+            else:
+                if prompt not in (None, "", [""] * batch_size) or prompt_ids is not None:
+                    raise EegclipError("no text encoder in this pipeline: pass text_encoder= / text_encoder_2= (clip_text.sdxl_text_encoder(), "
+                                       "sdxl_text_encoder_2()), or prompt_embeds / pooled_prompt_embeds, or the empty prompt the reference uses")
+                prompt_embeds = self.empty_prompt_embeds.expand(batch_size, -1, -1)
+                pooled_prompt_embeds = self.empty_pooled_embeds.expand(batch_size, -1)
+        if do_classifier_free_guidance and negative_prompt_embeds is None:
+            if self.text_encoder is not None and (negative_prompt is not None or negative_prompt_ids is not None):
+                negative_prompt_embeds, negative_pooled_prompt_embeds = self._encode_text(negative_prompt, negative_prompt_2, batch_size, clip_skip,
+                                                                                          negative_prompt_ids)
+                if negative_prompt_embeds.shape != prompt_embeds.shape:
+                    raise EegclipError(f"negative prompt embeds {tuple(negative_prompt_embeds.shape)}, prompt embeds {tuple(prompt_embeds.shape)}")
+            else:                                                                 # (no negative prompt embeds to zeros under force_zeros_for_empty_prompt)
+                negative_prompt_embeds = torch.zeros_like(prompt_embeds)
+                negative_pooled_prompt_embeds = torch.zeros_like(pooled_prompt_embeds)
         return prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds
 
     def prepare_latents(self, batch_size, channels, height, width, dtype, device, generator, latents=None):
@@ -722,7 +795,7 @@ def generate_ip_adapter_embeds(self, prompt=None, prompt_2=None, height=None, wi
                                cross_attention_kwargs=None, guidance_rescale=0.0, original_size=None, crops_coords_top_left=(0, 0), target_size=None,
                                negative_original_size=None, negative_crops_coords_top_left=(0, 0), negative_target_size=None, clip_skip=None,
                                callback_on_step_end=None, callback_on_step_end_tensor_inputs=("latents",), img2img_strength=1.0, low_level_image=None,
-                               low_level_latent=None, **kwargs):
+                               low_level_latent=None, prompt_ids=None, negative_prompt_ids=None, **kwargs):
     """The reference's sampling loop (Generation/custom_pipeline.py:5-442; the three low-level arguments: custom_pipeline_low_level.py:56-560) over a
     pipeline object `self` (StandInSDXLPipeline here).  Same order of operations: encode prompt -> timesteps (-> img2img start) -> latents ->
     micro-conditioning ids -> [negative | positive] batch under classifier-free guidance, zeros as the negative image embedding -> loop:
@@ -740,13 +813,23 @@ def generate_ip_adapter_embeds(self, prompt=None, prompt_2=None, height=None, wi
         batch_size = 1
     elif prompt is not None and isinstance(prompt, list):
         batch_size = len(prompt)
-    else:
+    elif prompt_embeds is not None:
         batch_size = prompt_embeds.shape[0]
+    elif prompt_ids is not None:
+        batch_size = len(prompt_ids[0])
+    else:
+        raise EegclipError("generate_ip_adapter_embeds needs prompt, prompt_embeds or prompt_ids")
     if ip_adapter_embeds is not None and prompt_embeds is None and ip_adapter_embeds.shape[0] != batch_size and isinstance(prompt, str):
         batch_size = ip_adapter_embeds.shape[0]                  # several image embeddings with the one (empty) prompt: one image each
     device, dtype = self.device, self.dtype
+    text_kw = {}
+    if getattr(self, "text_encoder", None) is not None:                      # (a pipeline without encoders keeps the narrower encode_prompt signature)
+        text_kw = dict(prompt_2=prompt_2, negative_prompt=negative_prompt, negative_prompt_2=negative_prompt_2, clip_skip=clip_skip, prompt_ids=prompt_ids,
+                       negative_prompt_ids=negative_prompt_ids)
+    elif prompt_ids is not None:
+        raise EegclipError("prompt_ids needs a pipeline with text encoders")
     prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds = self.encode_prompt(
-        prompt, batch_size, prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds, negative_pooled_prompt_embeds, do_cfg)
+        prompt, batch_size, prompt_embeds, pooled_prompt_embeds, negative_prompt_embeds, negative_pooled_prompt_embeds, do_cfg, **text_kw)
     # 4. timesteps (+ the img2img start of the low-level variant: skip the first (1 - strength) fraction of the schedule)
     timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, timesteps)
     t_start = 0

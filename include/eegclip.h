@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 13
+#define EEGCLIP_ABI_VERSION 14
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -442,6 +442,10 @@ int eegclip_cross_attn_fwd(const void* q, const void* k, const void* v, const vo
 int eegclip_self_attn_supported(int head_dim, long long ldq, long long ldk, long long ldv, long long ldo);
 int eegclip_self_attn_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B,
                           int Tq, int Tk, int heads, int head_dim, float scale, int dtype, void* stream);
+/* the causal form (CLIP's text encoders; transformers' CLIPAttention with the causal mask alone): key j contributes to query i only if j <= i.  Same arguments
+ * and requirements, and Tq == Tk (anything else: EEGCLIP_EINVAL).  Key tiles past a workgroup's last query are neither loaded nor multiplied. */
+int eegclip_self_attn_causal_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B,
+                                 int Tq, int Tk, int heads, int head_dim, float scale, int dtype, void* stream);
 
 /* ---- retrieval readouts.  ATMS_retrieval.py:246 (argmax), :320 (top-5).  ties -> lowest index; out_idx: int64 (rows, k), k <= 8 */
 int eegclip_topk_rows(const float* X, int rows, int cols, long long ld, int k, const float* scale /* device scalar or NULL: rank by scale*x */,
@@ -647,6 +651,19 @@ int eegclip_layernorm16(const void* x, long long ldx, const void* gamma, const v
                         void* stream);
 int eegclip_geglu16(const void* x, void* y, int M, int D, int dtype, void* stream);
 int eegclip_concat16(const void* a, const void* b, void* out, int N, int H, int W, int pad, int Ca, int Cb, int out_pad, int dtype, void* stream);
+
+/* ---- SDXL's CLIP text encoders (csrc/clip_text.hip; Generation/custom_pipeline.py:296-316 encode_prompt, :456-492 loads text_encoder / text_encoder_2 with
+ * stabilityai/sdxl-turbo; the modules are transformers' CLIPTextModel / CLIPTextModelWithProjection), 16-bit in and out, fp32 arithmetic.  Their GEMMs are
+ * eegclip_gemm16, their LayerNorms eegclip_layernorm16, their attention eegclip_self_attn_causal_fwd.
+ *   eegclip_gather_rows16  out[r] = table[idx[r]] (+ add[r % add_rows], one fp32 addition rounded once; add may be NULL) for r < rows: dense rows of C elements
+ *                          (C % 8 == 0), table (table_rows, C), add (add_rows, C), idx int32 (idx64 = 0) or int64 (idx64 = 1) on the device.  An index outside
+ *                          [0, table_rows) is clamped into it, never read through.  The embedding (token_embedding[ids] + position_embedding[t]) and the
+ *                          pooling (the row of each prompt's end-of-text token).
+ *   eegclip_act16          y[m][j] = act(x[m][j]), j < D (D % 8 == 0; row strides ldx / ldy, multiples of 8; y may be x): kind 0 = x * sigmoid(1.702 x)
+ *                          (transformers' quick_gelu), kind 1 = 0.5 x (1 + erf(x / sqrt 2)) (gelu) */
+int eegclip_gather_rows16(const void* table, long long table_rows, const void* idx, int idx64, const void* add, int add_rows, void* out, int rows, int C,
+                          int dtype, void* stream);
+int eegclip_act16(const void* x, long long ldx, void* y, long long ldy, int M, int D, int kind, int dtype, void* stream);
 
 /* ---- the projection head's GEMMs at M = the batch (csrc/head_gemm.hip; Retrieval/ATMS_retrieval.py:157-167 forward, its input gradients, and the query
  * gradient of the loss, models/loss.py:122-140): C[m][n] = sum_k A[m][k] B[n][k] from k-contiguous bf16 hi | lo planes like eegclip_gemm_planes, but
