@@ -11,19 +11,20 @@ them in fp32 torch and tests/test_clip_text_layout.py pins that restatement to t
                 x = x + fc2(act(fc1(layer_norm2(x))));  hidden_states.append(x)            act: quick_gelu = x sigmoid(1.702 x), or erf gelu
     last_hidden_state = final_layer_norm(x);  pooler_output = last_hidden_state[b, argmax_t ids[b]];  text_embeds = text_projection(pooler_output)
 
-Arithmetic (no library GEMM, no torch math op, no eager fallback; bit-reproducible): csrc/clip_text.hip gather_rows16 for the embedding and the pooling,
+Arithmetic (the wrappers of ops16.py; no library GEMM, no torch math op, no eager fallback; bit-reproducible): csrc/clip_text.hip gather_rows16 for the embedding and the pooling,
 csrc/unet.hip layernorm16, ONE csrc/gemm16.hip launch for q | k | v over a packed weight, the causal form of csrc/self_attn.hip reading that (B T, 3C)
 buffer in place, out_proj / fc2 with the residual in the GEMM epilogue, csrc/clip_text.hip act16 between fc1 and fc2.  The nn.Embedding / nn.Linear /
 nn.LayerNorm children hold parameters only (the published checkpoints' state_dict keys); they are never called.
 """
 import json
 import unicodedata
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
-from ._lib import EegclipError, check, lib, raw_stream, require_cuda
-from .sdxl import _dt, linear16, self_attention
+from ._lib import EegclipError, require_cuda
+from .ops16 import PackedWeights, act16, gather_rows16, layernorm16, linear16, seeded_parameters, self_attention
 
 BOS_ID, EOS_ID = 49406, 49407                  # <|startoftext|>, <|endoftext|> in CLIP's vocabulary (the two highest ids)
 ACT_KINDS = {"quick_gelu": 0, "gelu": 1}
@@ -71,10 +72,6 @@ class _TextTransformer(nn.Module):
         self.final_layer_norm = nn.LayerNorm(c, eps=eps)
 
 
-class _Config:
-    pass
-
-
 class CLIPTextOutput:
     """What diffusers' encode_prompt reads from a transformers output: out[0] (text_embeds with a projection, else last_hidden_state), .hidden_states,
     .last_hidden_state, .pooler_output, .text_embeds.  Indexing skips the fields that are None, as transformers' ModelOutput does."""
@@ -106,23 +103,15 @@ class CLIPTextEncoder(nn.Module):
             raise EegclipError("CLIPTextEncoder: hidden_size, intermediate_size and projection_dim must be multiples of 128 (csrc/gemm16.hip)")
         if hidden_act not in ACT_KINDS:
             raise EegclipError(f"CLIPTextEncoder: hidden_act must be one of {sorted(ACT_KINDS)}; got {hidden_act!r}")
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise EegclipError("CLIPTextEncoder runs in fp16 or bf16")
-        cfg = self.config = _Config()
+        cfg = self.config = SimpleNamespace()
         cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers, cfg.num_attention_heads = hidden_size, intermediate_size, num_hidden_layers, num_attention_heads
         cfg.hidden_act, cfg.projection_dim, cfg.vocab_size, cfg.max_position_embeddings = hidden_act, projection_dim, vocab_size, max_position_embeddings
         cfg.layer_norm_eps, cfg.eos_token_id, cfg.bos_token_id = layer_norm_eps, 2, 0            # (SDXL's configs: eos_token_id 2 -> argmax pooling)
-        dev = torch.device(device) if device is not None else torch.device("cpu")
-        rng_devs = [dev.index if dev.index is not None else torch.cuda.current_device()] if dev.type == "cuda" else []
-        with torch.random.fork_rng(devices=rng_devs), dev:
-            torch.manual_seed(seed)
+        with seeded_parameters(self, dtype, device, seed):
             self.text_model = _TextTransformer(vocab_size, max_position_embeddings, hidden_size, intermediate_size, num_hidden_layers, layer_norm_eps)
             if projection_dim is not None:
                 self.text_projection = nn.Linear(hidden_size, projection_dim, bias=False)
-        self.to(dtype)
-        for p in self.parameters():
-            p.requires_grad_(False)
-        self._cache = {}
+        self._cache = PackedWeights()
 
     @property
     def dtype(self):
@@ -132,39 +121,12 @@ class CLIPTextEncoder(nn.Module):
     def device(self):
         return self.text_model.final_layer_norm.weight.device
 
-    # ---- packed q | k | v: keyed on the parameters' identity, version and address (load_state_dict / in-place edits / .data swaps repack) -------------
-    def _packed_of(self, tag, params, make):
-        key = tuple((id(p), p._version, p.data_ptr()) for p in params)
-        hit = self._cache.get(tag)
-        if hit is None or hit[0] != key:
-            hit = self._cache[tag] = (key, params, make())            # (holds the parameters: their ids cannot be recycled while the entry lives)
-        return hit[2]
-
     def _qkv(self, i, a):
         ps = [a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.q_proj.bias, a.k_proj.bias, a.v_proj.bias]
-        return self._packed_of(("qkv", i), ps, lambda: (torch.cat([p.detach() for p in ps[:3]], 0).contiguous(),
+        return self._cache.get(("qkv", i), ps, lambda: (torch.cat([p.detach() for p in ps[:3]], 0).contiguous(),
                                                           torch.cat([p.detach() for p in ps[3:]], 0).contiguous()))
 
     # ---- layers -------------------------------------------------------------------------------------------------------------------------------------
-    def _ln(self, x, mod):
-        M, C = x.shape
-        y = torch.empty_like(x)
-        check(lib().eegclip_layernorm16(x.data_ptr(), x.stride(0), mod.weight.data_ptr(), mod.bias.data_ptr(), y.data_ptr(), C, M, C, float(mod.eps),
-                                        _dt(x), raw_stream()), "layernorm16")
-        return y
-
-    def _gather(self, table, idx, rows, add=None, add_rows=0):
-        C = table.shape[1]
-        out = torch.empty(rows, C, dtype=table.dtype, device=table.device)
-        check(lib().eegclip_gather_rows16(table.data_ptr(), table.shape[0], idx.data_ptr(), 1, add.data_ptr() if add is not None else None, add_rows,
-                                          out.data_ptr(), rows, C, _dt(table), raw_stream()), "gather_rows16")
-        return out
-
-    def _act(self, f):
-        M, D = f.shape
-        check(lib().eegclip_act16(f.data_ptr(), f.stride(0), f.data_ptr(), f.stride(0), M, D, ACT_KINDS[self.config.hidden_act], _dt(f), raw_stream()), "act16")
-        return f
-
     def _ids(self, input_ids):
         """ids arrive as host data (a tokenizer's output); a device tensor is copied back: every id is range-checked before a kernel indexes with it"""
         ids = torch.as_tensor(input_ids).detach().to("cpu")
@@ -197,23 +159,24 @@ class CLIPTextEncoder(nn.Module):
         n_run = L if num_layers is None else int(num_layers)
         if not 0 <= n_run <= L:
             raise EegclipError(f"num_layers must be in [0, {L}]; got {num_layers}")
-        dev = self.device
-        x = self._gather(emb.token_embedding.weight, ids.reshape(-1).to(dev), B * T, emb.position_embedding.weight, T)
+        dev, act = self.device, ACT_KINDS[cfg.hidden_act]
+        ln = lambda x, mod: layernorm16(x, mod.weight, mod.bias, mod.eps)
+        x = gather_rows16(emb.token_embedding.weight, ids.reshape(-1).to(dev), B * T, emb.position_embedding.weight, T)
         hs = [x]
         for i, layer in enumerate(self.text_model.encoder.layers[:n_run]):
             a, mlp = layer.self_attn, layer.mlp
             w, b = self._qkv(i, a)
-            qkv = linear16(self._ln(x, layer.layer_norm1), w, b).reshape(B, T, 3 * C)
+            qkv = linear16(ln(x, layer.layer_norm1), w, b).reshape(B, T, 3 * C)
             o = self_attention(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], heads, causal=True)
             x = linear16(o.reshape(B * T, C), a.out_proj.weight, a.out_proj.bias, x)
-            f = self._act(linear16(self._ln(x, layer.layer_norm2), mlp.fc1.weight, mlp.fc1.bias))
+            f = act16(linear16(ln(x, layer.layer_norm2), mlp.fc1.weight, mlp.fc1.bias), act)
             x = linear16(f, mlp.fc2.weight, mlp.fc2.bias, x)
             hs.append(x)
         last = pooled = text_embeds = None
         if n_run == L:
-            last2 = self._ln(x, self.text_model.final_layer_norm)
+            last2 = ln(x, self.text_model.final_layer_norm)
             eos = (torch.arange(B) * T + ids.argmax(dim=-1)).to(dev)                    # first maximum: <|endoftext|> is the vocabulary's highest id
-            pooled = self._gather(last2, eos, B)
+            pooled = gather_rows16(last2, eos, B)
             last = last2.reshape(B, T, C)
             if cfg.projection_dim is not None:
                 text_embeds = linear16(pooled, self.text_projection.weight)

@@ -1,0 +1,284 @@
+"""The 16-bit host layer of the generation stack: what sdxl.py (processors, stand-in UNet), sdxl_unet.py, clip_text.py and vae.py share.
+
+* thin wrappers over the 16-bit entry points, free functions taking tensors: linear16 / linear (csrc/gemm16.hip, csrc/vae.hip conv16 as a 1 x 1
+  convolution), self_attention (csrc/self_attn.hip), cross_attention (csrc/cross_attn.hip), layernorm16 / geglu16 / concat16 (csrc/unet.hip),
+  act16 / gather_rows16 (csrc/clip_text.hip).  No library GEMM, no eager fallback: a shape a kernel does not take raises.
+* PackedWeights: the one cache of repacked weights and the one statement of its key.
+* seeded_parameters: the construction of a module whose nn children hold parameters only and are never called.
+* what both UNets do around their attention stacks: image_embeds_of, text_time_embedding, TokenKV.
+
+`lib`, `require_cuda` and `raw_stream` are called as this module's globals: tests/emu_patch.py swaps them to run these wrappers on the lane emulator.
+"""
+import contextlib
+import math
+import typing
+
+import torch
+
+from . import _abi
+from ._lib import EegclipError, check, lib, raw_stream, require_cuda
+
+_CODES = {torch.float16: _abi.DT_F16, torch.bfloat16: _abi.DT_BF16}
+
+
+def dtype_code(t):
+    """the C ABI's dtype code of a tensor or a torch.dtype"""
+    dtype = t.dtype if isinstance(t, torch.Tensor) else t
+    code = _CODES.get(dtype) if isinstance(dtype, torch.dtype) else None
+    if code is None:
+        raise EegclipError(f"the 16-bit kernels run in fp16 or bf16 (the pipeline dtype of the reference: custom_pipeline.py:459, "
+                           f"custom_pipeline_low_level.py:576); got {dtype!r}")
+    return code
+
+
+# ---------------------------------------------------------------------------------------------------------------------- kernel wrappers
+def linear16(x, weight, bias=None, residual=None, r_div=0):
+    """y = x @ weight.T (+ bias) (+ residual) on the 16-bit matrix cores.  x (..., K), weight (N, K) (nn.Linear layout), residual shaped like y,
+    or (rows / r_div, N) with r_div > 0 (one row per block of r_div consecutive rows: a per-sample embedding).  N % 128 == 0, K % 64 == 0."""
+    require_cuda(x, "x")
+    dt = dtype_code(x)
+    K = x.shape[-1]
+    N = weight.shape[0]
+    if weight.shape[1] != K or weight.dtype != x.dtype:
+        raise EegclipError(f"linear16: weight {tuple(weight.shape)} {weight.dtype} does not match input (..., {K}) {x.dtype}")
+    if N % 128 or K % 64:
+        raise EegclipError(f"linear16 takes N % 128 == 0 and K % 64 == 0 (got N = {N}, K = {K}); pad the layer")
+    x2 = x.reshape(-1, K)
+    if x2.stride(1) != 1 or x2.stride(0) % 8:
+        x2 = x2.contiguous()
+    w = weight if weight.is_contiguous() else weight.contiguous()
+    M = x2.shape[0]
+    out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+    r2 = None
+    if residual is not None:
+        r2 = residual.reshape(-1, N)
+        if r2.stride(1) != 1 or r2.stride(0) % 4:
+            r2 = r2.contiguous()
+        if r2.shape[0] != (M if r_div == 0 else (M + r_div - 1) // r_div):
+            raise EegclipError("linear16: residual rows do not match")
+    b = bias.contiguous() if bias is not None else None
+    check(lib().eegclip_gemm16(x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), N, b.data_ptr() if b is not None else None,
+                               r2.data_ptr() if r2 is not None else None, r2.stride(0) if r2 is not None else 0, int(r_div), M, N, K, dt, raw_stream()), "gemm16")
+    return out.reshape(*x.shape[:-1], N)
+
+
+def linear(x, weight, bias=None, residual=None):
+    """x (M, K) rows -> (M, N) = x W^T + b (+ residual): gemm16 when N % 128 == 0, else conv16 as a 1 x 1 convolution over M pixels (Cout % 64)"""
+    N = weight.shape[0]
+    if N % 128 == 0:
+        return linear16(x, weight, bias, residual)
+    M, K = x.shape
+    x = x.contiguous()
+    out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+    r = residual.contiguous() if residual is not None else None
+    d = _abi.Conv16Desc(in_=x.data_ptr(), W=weight.data_ptr(), out=out.data_ptr(), bias=bias.data_ptr() if bias is not None else None,
+                        residual=r.data_ptr() if r is not None else None, N=1, Hi=M, Wi=1, Cin=K, in_pad=0, Ho=M, Wo=1, Cout=N, out_pad=0, KS=1, stride=1,
+                        pad_top=0, pad_left=0, upsample=0, dtype=dtype_code(x))
+    check(lib().eegclip_conv16(d, raw_stream()), "conv16 (1 x 1 linear)")
+    return out
+
+
+def cross_attention(q, k, v, heads, k_ip=None, v_ip=None, ip_scale=1.0):
+    """softmax(q k^T/8) v + ip_scale * softmax(q k_ip^T/8) v_ip, head_dim 64.  q (B,HW,C); k,v (B,S,C); k_ip,v_ip (B,S_ip,C)."""
+    require_cuda(q, "q")
+    dt = dtype_code(q)
+    B, HW, C = q.shape
+    if C != heads * 64:
+        raise EegclipError(f"head_dim must be 64 (C={C}, heads={heads})")
+    q, k, v = q.contiguous(), k.to(q.dtype).contiguous(), v.to(q.dtype).contiguous()
+    S = k.shape[1]
+    S_ip = 0
+    kp = vp = None
+    if k_ip is not None:
+        k_ip, v_ip = k_ip.to(q.dtype).contiguous(), v_ip.to(q.dtype).contiguous()
+        S_ip = k_ip.shape[1]
+        kp, vp = k_ip.data_ptr(), v_ip.data_ptr()
+    out = torch.empty_like(q)
+    check(lib().eegclip_cross_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), kp, vp, out.data_ptr(), B, HW, heads, 64, S, S_ip,
+                                       float(ip_scale), dt, raw_stream()), "cross_attn_fwd")
+    return out
+
+
+def _row_layout(t, name):
+    """(B, T, C) view -> (tensor, row stride in elements) as csrc/self_attn.hip addresses it: unit column stride, sample b's rows from b * T * ld.
+    Column slices of a fused (B, T, 3C) projection qualify as they are; anything else is made contiguous first."""
+    B, T, C = t.shape
+    ld = t.stride(1) if T > 1 else (t.stride(0) if B > 1 else C)
+    if t.stride(2) != 1 or (B > 1 and t.stride(0) != T * ld) or ld < C or ld % 8 or t.data_ptr() % 16:
+        if name == "out":
+            raise EegclipError("self_attention: `out` must be (B, T, C) rows with unit column stride, a row stride that is a multiple of 8 and a "
+                               "16-byte aligned base")
+        t = t.contiguous()
+        ld = C
+    return t, ld
+
+
+def self_attention(q, k, v, heads, scale=None, out=None, causal=False):
+    """softmax(scale * q k^T) v per head of 64 (flash-style, csrc/self_attn.hip: no T x T buffer).  q (B, Tq, C), k / v (B, Tk, C), C = heads * 64,
+    fp16 or bf16; the three may be column slices of one fused (B, T, 3C) projection (consumed in place).  scale defaults to 1/8 (diffusers'
+    attn.scale).  causal: key j reaches query i only if j <= i (CLIP's text encoders; Tq == Tk).  Returns `out` (B, Tq, C), which may be given."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        require_cuda(t, n)
+    if q.dtype not in _CODES or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise EegclipError(f"self_attention runs in fp16 or bf16 with one dtype for q, k, v (got {q.dtype}, {k.dtype}, {v.dtype})")
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise EegclipError("self_attention takes (B, T, C) tensors")
+    B, Tq, C = q.shape
+    Tk = k.shape[1]
+    if C != heads * 64:
+        raise EegclipError(f"head_dim must be 64 (C={C}, heads={heads})")
+    if tuple(k.shape) != (B, Tk, C) or tuple(v.shape) != (B, Tk, C):
+        raise EegclipError(f"self_attention: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
+    if B * Tq * Tk == 0:
+        raise EegclipError("self_attention: empty input")
+    if causal and Tq != Tk:
+        raise EegclipError(f"self_attention: the causal form takes Tq == Tk (got {Tq}, {Tk})")
+    q, ldq = _row_layout(q, "q")
+    k, ldk = _row_layout(k, "k")
+    v, ldv = _row_layout(v, "v")
+    if out is None:
+        out = torch.empty(B, Tq, C, dtype=q.dtype, device=q.device)
+    elif tuple(out.shape) != (B, Tq, C) or out.dtype != q.dtype or out.device != q.device:
+        raise EegclipError(f"self_attention: out {tuple(out.shape)} {out.dtype} does not match ({B}, {Tq}, {C}) {q.dtype}")
+    out, ldo = _row_layout(out, "out")
+    scale = 1.0 / math.sqrt(64) if scale is None else float(scale)
+    fwd = lib().eegclip_self_attn_causal_fwd if causal else lib().eegclip_self_attn_fwd
+    check(fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, B, Tq, Tk, heads, 64, scale, _CODES[q.dtype], raw_stream()),
+          "self_attn_causal_fwd" if causal else "self_attn_fwd")
+    return out
+
+
+def layernorm16(x, weight, bias, eps):
+    """LayerNorm over the rows of x (M, C)"""
+    M, C = x.shape
+    y = torch.empty_like(x)
+    check(lib().eegclip_layernorm16(x.data_ptr(), x.stride(0), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), C, M, C, float(eps), dtype_code(x),
+                                    raw_stream()), "layernorm16")
+    return y
+
+
+def geglu16(f):
+    """f (M, 2 D) = [a | g] -> a * gelu_erf(g) (M, D)"""
+    M, D2 = f.shape
+    y = torch.empty(M, D2 // 2, dtype=f.dtype, device=f.device)
+    check(lib().eegclip_geglu16(f.data_ptr(), y.data_ptr(), M, D2 // 2, dtype_code(f), raw_stream()), "geglu16")
+    return y
+
+
+def act16(f, kind):
+    """f (M, D) -> act(f) in place; kind: 0 quick_gelu, 1 erf gelu (clip_text.ACT_KINDS)"""
+    M, D = f.shape
+    check(lib().eegclip_act16(f.data_ptr(), f.stride(0), f.data_ptr(), f.stride(0), M, D, kind, dtype_code(f), raw_stream()), "act16")
+    return f
+
+
+def gather_rows16(table, idx, rows, add=None, add_rows=0):
+    """out[r] = table[idx[r]] (+ add[r % add_rows]): the token + position embedding, and the pooling"""
+    C = table.shape[1]
+    out = torch.empty(rows, C, dtype=table.dtype, device=table.device)
+    check(lib().eegclip_gather_rows16(table.data_ptr(), table.shape[0], idx.data_ptr(), 1, add.data_ptr() if add is not None else None, add_rows,
+                                      out.data_ptr(), rows, C, dtype_code(table), raw_stream()), "gather_rows16")
+    return out
+
+
+def concat16(a, b, out):
+    """padded NHWC frames a (N, H + 2, W + 2, Ca), b (.., Cb) -> the caller's frame `out` (.., Ca + Cb): the skip concatenation"""
+    N, Hp, Wp, Ca = a.shape
+    check(lib().eegclip_concat16(a.data_ptr(), b.data_ptr(), out.data_ptr(), N, Hp - 2, Wp - 2, 1, Ca, b.shape[3], 1, dtype_code(a), raw_stream()), "concat16")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------- modules and their weights
+class PackedWeights:
+    """Repacked weights (concatenated q | k | v, stacked time_emb_proj, convolution weights in the kernel's order), made once per state of the
+    parameters they come from.  The key is (id, _version, data_ptr) per parameter: identity and version catch load_state_dict and in-place edits, the
+    address a `.data =` swap (same object, same version).  The entry holds the parameters themselves, so their ids cannot be recycled for other
+    tensors while it lives.  None entries (optional biases) are part of the key."""
+
+    def __init__(self):
+        self._entries = {}
+
+    @staticmethod
+    def key(params):
+        return tuple((id(p), p._version, p.data_ptr()) if p is not None else None for p in params)
+
+    def get(self, tag, params, make):
+        key = self.key(params)
+        hit = self._entries.get(tag)
+        if hit is None or hit[0] != key:
+            hit = self._entries[tag] = (key, params, make())
+        return hit[2]
+
+
+@contextlib.contextmanager
+def seeded_parameters(module, dtype, device=None, seed=0):
+    """Build `module`'s children inside the block: PyTorch's default initialisation under `seed` on `device` (the caller's RNG streams are left as they
+    were); afterwards the module is cast to `dtype` (fp16 / bf16) and frozen.  For modules whose nn children hold parameters only."""
+    dtype_code(dtype)
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    rng_devs = [dev.index if dev.index is not None else torch.cuda.current_device()] if dev.type == "cuda" else []
+    with torch.random.fork_rng(devices=rng_devs), dev:
+        torch.manual_seed(seed)
+        yield
+    module.to(dtype)
+    for p in module.parameters():
+        p.requires_grad_(False)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- shared by the two UNets
+def _sinusoid(t, dim, flip_sin_to_cos=True):
+    """diffusers Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0): [cos | sin] of t * exp(-ln(1e4) i / (dim/2))"""
+    half = dim // 2
+    freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32, device=t.device) / half)
+    arg = t.float()[..., None] * freqs
+    return torch.cat([arg.cos(), arg.sin()] if flip_sin_to_cos else [arg.sin(), arg.cos()], dim=-1)
+
+
+def image_embeds_of(added_cond_kwargs):
+    """added_cond_kwargs["image_embeds"] as (B, dim) or None: diffusers passes a list of (B, n_images, dim) tensors, one per adapter"""
+    e = (added_cond_kwargs or {}).get("image_embeds")
+    if isinstance(e, (list, tuple)):
+        e = e[0]
+    return e[:, 0] if e is not None and e.dim() == 3 else e
+
+
+def text_time_embedding(timestep, B, added, time_mlp, add_mlp, time_dim, add_dim, dtype, device):
+    """silu(time_embedding(Timesteps(time_dim)(t)) + add_embedding(cat(text_embeds, Timesteps(add_dim)(time_ids)))): (B, 4 C0), what every time
+    projection reads (addition_embed_type "text_time").  time_mlp / add_mlp: (w1, b1, w2, b2) of linear_1, SiLU, linear_2; the biases may be None."""
+    if added is None or "text_embeds" not in added or "time_ids" not in added:
+        raise EegclipError("the UNet needs added_cond_kwargs with 'text_embeds' and 'time_ids' (addition_embed_type 'text_time')")
+    silu = torch.nn.functional.silu
+    t = torch.as_tensor(timestep, device=device).reshape(-1).float().expand(B)
+    w1, b1, w2, b2 = time_mlp
+    e = linear16(silu(linear16(_sinusoid(t, time_dim).to(dtype), w1, b1)), w2, b2)
+    text_embeds = added["text_embeds"].to(device=device, dtype=dtype)
+    time_ids = added["time_ids"].to(device=device)
+    aug = torch.cat([text_embeds, _sinusoid(time_ids.flatten(), add_dim).reshape(B, -1).to(dtype)], dim=-1)          # (B, 1280 + 6 * 256) in SDXL
+    w1, b1, w2, b2 = add_mlp
+    if aug.shape[1] != w1.shape[1]:
+        raise EegclipError(f"text_embeds + time_ids give {aug.shape[1]} features; add_embedding takes {w1.shape[1]}")
+    return silu(e + linear16(silu(linear16(aug, w1, b1)), w2, b2))
+
+
+class TokenKV(typing.NamedTuple):
+    """K / V of the text tokens (and of the IP-Adapter's image tokens) at every cross-attention position: they do not change between denoising steps, so
+    they are projected once per sampling run.  `entries` is the list of (k, v, k_ip, v_ip) per position.  A hit needs THE SAME two token tensors
+    (identity and _version; the entry holds them, so an address recycled by the allocator cannot match) and an equal `extra` (the caller's: batch
+    size, key of the projection weights).  A UNet's `_kv` is one of these, or None before the first projection."""
+    text: torch.Tensor
+    text_version: int
+    image: typing.Optional[torch.Tensor]
+    image_version: typing.Optional[int]
+    extra: object
+    entries: list
+
+    @classmethod
+    def project(cls, text_src, image_src, extra, text, ip, weights):
+        """weights: (to_k, to_v, to_k_ip, to_v_ip) per position; text (B, S, X) / ip (B, S_ip, X) or None: the token matrices of the two sources"""
+        entries = [(linear16(text, wk), linear16(text, wv)) + ((linear16(ip, wki), linear16(ip, wvi)) if ip is not None else (None, None))
+                   for wk, wv, wki, wvi in weights]
+        return cls(text_src, text_src._version, image_src, None if image_src is None else image_src._version, extra, entries)
+
+    def hit(self, text_src, image_src, extra):
+        return self.text is text_src and self.text_version == text_src._version and self.image is image_src and \
+            self.image_version == (None if image_src is None else image_src._version) and self.extra == extra

@@ -3,7 +3,7 @@
 What the reference does there: `generate_ip_adapter_embeds` is diffusers' SDXL sampling loop with
 one extra input -- the EEG-predicted CLIP image embedding, fed to the UNet's cross-attention through the IP-Adapter -- and
 `Generator4Embeds` wraps sdxl-turbo around it.  diffusers and every checkpoint are third-party and absent offline, so this module is
-self-contained:
+self-contained (the kernel wrappers linear16 / cross_attention / self_attention live in ops16.py and are importable from here as before):
 
 * cross_attention(...) / HIPIPAdapterAttnProcessor   the UNet cross-attention with the IP-Adapter branch in ONE kernel (csrc/cross_attn.hip);
                                                      q / k / v / out projections on the 16-bit MFMA GEMM (csrc/gemm16.hip), K and V of the
@@ -27,80 +27,21 @@ self-contained:
                                                      text_encoder= / text_encoder_2= (clip_text.py): encode_prompt as diffusers' SDXL pipeline does it.
 """
 import math
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
-from . import _abi
 from ._lib import EegclipError, check, lib, raw_stream, require_cuda
+from .ops16 import PackedWeights, TokenKV, cross_attention, dtype_code, image_embeds_of, linear16, self_attention, text_time_embedding
 
 
-def _stream():
-    return raw_stream()
-
-
-def _dt(t):
-    if t.dtype == torch.float16:
-        return _abi.DT_F16
-    if t.dtype == torch.bfloat16:
-        return _abi.DT_BF16
-    raise EegclipError("the SDXL path runs in fp16 or bf16 (the pipeline dtype of the reference: custom_pipeline.py:459, custom_pipeline_low_level.py:576)")
-
-
-def linear16(x, weight, bias=None, residual=None, r_div=0):
-    """y = x @ weight.T (+ bias) (+ residual) on the 16-bit matrix cores.  x (..., K), weight (N, K) (nn.Linear layout), residual shaped like y,
-    or (rows / r_div, N) with r_div > 0 (one row per block of r_div consecutive rows: a per-sample embedding).  N % 128 == 0, K % 64 == 0."""
-    require_cuda(x, "x")
-    dt = _dt(x)
-    K = x.shape[-1]
-    N = weight.shape[0]
-    if weight.shape[1] != K or weight.dtype != x.dtype:
-        raise EegclipError(f"linear16: weight {tuple(weight.shape)} {weight.dtype} does not match input (..., {K}) {x.dtype}")
-    if N % 128 or K % 64:
-        raise EegclipError(f"linear16 takes N % 128 == 0 and K % 64 == 0 (got N = {N}, K = {K}); pad the layer")
-    x2 = x.reshape(-1, K)
-    if x2.stride(1) != 1 or x2.stride(0) % 8:
-        x2 = x2.contiguous()
-    w = weight if weight.is_contiguous() else weight.contiguous()
-    M = x2.shape[0]
-    out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-    r2 = None
-    if residual is not None:
-        r2 = residual.reshape(-1, N)
-        if r2.stride(1) != 1 or r2.stride(0) % 4:
-            r2 = r2.contiguous()
-        if r2.shape[0] != (M if r_div == 0 else (M + r_div - 1) // r_div):
-            raise EegclipError("linear16: residual rows do not match")
-    b = bias.contiguous() if bias is not None else None
-    check(lib().eegclip_gemm16(x2.data_ptr(), x2.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), N, b.data_ptr() if b is not None else None,
-                               r2.data_ptr() if r2 is not None else None, r2.stride(0) if r2 is not None else 0, int(r_div), M, N, K, dt, _stream()), "gemm16")
-    return out.reshape(*x.shape[:-1], N)
-
-
-def cross_attention(q, k, v, heads, k_ip=None, v_ip=None, ip_scale=1.0):
-    """softmax(q k^T/8) v + ip_scale * softmax(q k_ip^T/8) v_ip, head_dim 64.  q (B,HW,C); k,v (B,S,C); k_ip,v_ip (B,S_ip,C)."""
-    require_cuda(q, "q")
-    if q.dtype not in (torch.float16, torch.bfloat16):
-        raise EegclipError("cross_attention runs in fp16 or bf16 (the SDXL pipeline dtype)")
-    B, HW, C = q.shape
-    if C != heads * 64:
-        raise EegclipError(f"head_dim must be 64 (C={C}, heads={heads})")
-    q, k, v = q.contiguous(), k.to(q.dtype).contiguous(), v.to(q.dtype).contiguous()
-    S = k.shape[1]
-    S_ip = 0
-    kp = vp = None
-    if k_ip is not None:
-        k_ip, v_ip = k_ip.to(q.dtype).contiguous(), v_ip.to(q.dtype).contiguous()
-        S_ip = k_ip.shape[1]
-        kp, vp = k_ip.data_ptr(), v_ip.data_ptr()
-    out = torch.empty_like(q)
-    check(lib().eegclip_cross_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), kp, vp, out.data_ptr(), B, HW, heads, 64, S, S_ip,
-                                       float(ip_scale), _abi.DT_F16 if q.dtype == torch.float16 else _abi.DT_BF16, _stream()), "cross_attn_fwd")
-    return out
-
-
-def _hip_linear_ok(lin, x):
-    return lin.weight.shape[0] % 128 == 0 and lin.weight.shape[1] % 64 == 0 and lin.weight.dtype == x.dtype      # (linear16 itself rejects CPU tensors)
+def _lin(weight, x, bias=None, residual=None):
+    """linear16 (through this module's global: the tests count the processors' launches there) behind the processors' shape rule"""
+    if weight.shape[0] % 128 or weight.shape[1] % 64 or weight.dtype != x.dtype:
+        raise EegclipError(f"projection {tuple(weight.shape)} {weight.dtype} is outside the 16-bit GEMM's shapes (N % 128, K % 64, dtype of the "
+                           "activations); this processor issues no library GEMM")
+    return linear16(x, weight, bias, residual)
 
 
 class HIPIPAdapterAttnProcessor(nn.Module):
@@ -119,10 +60,7 @@ class HIPIPAdapterAttnProcessor(nn.Module):
 
     @staticmethod
     def _lin(layer, x, residual=None):
-        if not _hip_linear_ok(layer, x):
-            raise EegclipError(f"projection {tuple(layer.weight.shape)} {layer.weight.dtype} is outside the 16-bit GEMM's shapes (N % 128, K % 64, dtype of "
-                               "the activations); this processor issues no library GEMM")
-        return linear16(x, layer.weight, layer.bias, residual)
+        return _lin(layer.weight, x, layer.bias, residual)
 
     def begin_sampling_run(self):
         """Called by the sampling loop before its first UNet forward: inside one run the text / image tokens are constants (custom_pipeline.py:296-373
@@ -213,55 +151,6 @@ def install_cross_attention_processors(unet, scale=1.0):
     return unet
 
 
-def _row_layout(t, name):
-    """(B, T, C) view -> (tensor, row stride in elements) as csrc/self_attn.hip addresses it: unit column stride, sample b's rows from b * T * ld.
-    Column slices of a fused (B, T, 3C) projection qualify as they are; anything else is made contiguous first."""
-    B, T, C = t.shape
-    ld = t.stride(1) if T > 1 else (t.stride(0) if B > 1 else C)
-    if t.stride(2) != 1 or (B > 1 and t.stride(0) != T * ld) or ld < C or ld % 8 or t.data_ptr() % 16:
-        if name == "out":
-            raise EegclipError("self_attention: `out` must be (B, T, C) rows with unit column stride, a row stride that is a multiple of 8 and a "
-                               "16-byte aligned base")
-        t = t.contiguous()
-        ld = C
-    return t, ld
-
-
-def self_attention(q, k, v, heads, scale=None, out=None, causal=False):
-    """softmax(scale * q k^T) v per head of 64 (flash-style, csrc/self_attn.hip: no T x T buffer).  q (B, Tq, C), k / v (B, Tk, C), C = heads * 64,
-    fp16 or bf16; the three may be column slices of one fused (B, T, 3C) projection (consumed in place).  scale defaults to 1/8 (diffusers'
-    attn.scale).  causal: key j reaches query i only if j <= i (CLIP's text encoders; Tq == Tk).  Returns `out` (B, Tq, C), which may be given."""
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        require_cuda(t, n)
-    if q.dtype not in (torch.float16, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise EegclipError(f"self_attention runs in fp16 or bf16 with one dtype for q, k, v (got {q.dtype}, {k.dtype}, {v.dtype})")
-    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
-        raise EegclipError("self_attention takes (B, T, C) tensors")
-    B, Tq, C = q.shape
-    Tk = k.shape[1]
-    if C != heads * 64:
-        raise EegclipError(f"head_dim must be 64 (C={C}, heads={heads})")
-    if tuple(k.shape) != (B, Tk, C) or tuple(v.shape) != (B, Tk, C):
-        raise EegclipError(f"self_attention: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
-    if B * Tq * Tk == 0:
-        raise EegclipError("self_attention: empty input")
-    if causal and Tq != Tk:
-        raise EegclipError(f"self_attention: the causal form takes Tq == Tk (got {Tq}, {Tk})")
-    q, ldq = _row_layout(q, "q")
-    k, ldk = _row_layout(k, "k")
-    v, ldv = _row_layout(v, "v")
-    if out is None:
-        out = torch.empty(B, Tq, C, dtype=q.dtype, device=q.device)
-    elif tuple(out.shape) != (B, Tq, C) or out.dtype != q.dtype or out.device != q.device:
-        raise EegclipError(f"self_attention: out {tuple(out.shape)} {out.dtype} does not match ({B}, {Tq}, {C}) {q.dtype}")
-    out, ldo = _row_layout(out, "out")
-    scale = 1.0 / math.sqrt(64) if scale is None else float(scale)
-    fwd = lib().eegclip_self_attn_causal_fwd if causal else lib().eegclip_self_attn_fwd
-    check(fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, B, Tq, Tk, heads, 64, scale, _dt(q), _stream()),
-          "self_attn_causal_fwd" if causal else "self_attn_fwd")
-    return out
-
-
 class HIPAttnProcessor:
     """Self-attention (attn1) processor with diffusers' AttnProcessor2_0 call signature and arithmetic: q / k / v as ONE linear16 launch on the
     concatenated (3C, C) weight, one self_attention launch, to_out[0] as one linear16 with its bias and (attn.residual_connection) the residual
@@ -270,36 +159,23 @@ class HIPAttnProcessor:
     processor issues no library GEMM and has no fallback.
 
     The concatenated weight is cached per processor (one processor per layer: it costs the layer's 3 C^2 projection weights once more) and rebuilt
-    when any of to_q / to_k / to_v's weight or bias is replaced (identity) or edited in place (_version)."""
+    when any of to_q / to_k / to_v's weight or bias is replaced or edited in place (ops16.PackedWeights)."""
+
+    _lin = staticmethod(_lin)
 
     def __init__(self):
-        self._qkv = None
-
-    @staticmethod
-    def _params(attn):
-        return [attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, attn.to_q.bias, attn.to_k.bias, attn.to_v.bias]
+        self._qkv = PackedWeights()
 
     def _fused_qkv(self, attn):
-        ps = self._params(attn)
-        # identity + version decide; the address is compared as well so that a `.data =` swap (same object) cannot serve stale weights
-        key = tuple((id(p), p._version, p.data_ptr()) if p is not None else None for p in ps)
-        c = self._qkv
-        if c is not None and c[0] == key and all(a is b for a, b in zip(c[1], ps)):
-            return c[2], c[3]
-        w = torch.cat([p.detach() for p in ps[:3]], 0).contiguous()
-        b = None
-        if any(p is not None for p in ps[3:]):
-            b = torch.cat([p.detach() if p is not None else torch.zeros(ps[i].shape[0], dtype=w.dtype, device=w.device)
-                           for i, p in enumerate(ps[3:])], 0).contiguous()
-        self._qkv = (key, ps, w, b)                                     # (holds the parameters themselves: their ids cannot be recycled)
-        return w, b
+        ps = [attn.to_q.weight, attn.to_k.weight, attn.to_v.weight, attn.to_q.bias, attn.to_k.bias, attn.to_v.bias]
 
-    @staticmethod
-    def _lin(layer_weight, x, bias=None, residual=None):
-        if layer_weight.shape[0] % 128 or layer_weight.shape[1] % 64 or layer_weight.dtype != x.dtype:
-            raise EegclipError(f"projection {tuple(layer_weight.shape)} {layer_weight.dtype} is outside the 16-bit GEMM's shapes (N % 128, K % 64, "
-                               "dtype of the activations); this processor issues no library GEMM")
-        return linear16(x, layer_weight, bias, residual)
+        def make():
+            w = torch.cat([p.detach() for p in ps[:3]], 0).contiguous()
+            if all(p is None for p in ps[3:]):
+                return w, None
+            return w, torch.cat([p.detach() if p is not None else torch.zeros(ps[i].shape[0], dtype=w.dtype, device=w.device)
+                                 for i, p in enumerate(ps[3:])], 0).contiguous()
+        return self._qkv.get("qkv", ps, make)
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None, *args, **kwargs):
         if attention_mask is not None:
@@ -354,11 +230,8 @@ def _scaled_linear_alphas_cumprod(num_train_timesteps=1000, beta_start=0.00085, 
 class _SchedulerBase:
     order = 1
 
-    class _Cfg:
-        num_train_timesteps = 1000
-
     def __init__(self):
-        self.config = self._Cfg()
+        self.config = SimpleNamespace(num_train_timesteps=1000)
         self.alphas_cumprod = _scaled_linear_alphas_cumprod()
         self.timesteps = None
         self.num_inference_steps = None
@@ -371,7 +244,7 @@ class _SchedulerBase:
         check(lib().eegclip_sampler_step(x.data_ptr(), eps_u.contiguous().data_ptr(), eps_c.contiguous().data_ptr() if eps_c is not None else None,
                                          noise.contiguous().data_ptr() if noise is not None else None, out.data_ptr(),
                                          scaled.data_ptr() if scaled is not None else None, float(guidance), float(cx), float(ce), float(cn), float(in_scale),
-                                         x.numel(), _dt(x), _stream()), "sampler_step")
+                                         x.numel(), dtype_code(x), raw_stream()), "sampler_step")
         return out, scaled
 
 
@@ -456,14 +329,6 @@ def retrieve_timesteps(scheduler, num_inference_steps=None, device=None, timeste
 
 
 # ------------------------------------------------------------------------------------------------------------- stand-in UNet
-def _sinusoid(t, dim, flip_sin_to_cos=True):
-    """diffusers Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0): [cos | sin] of t * exp(-ln(1e4) i / (dim/2))"""
-    half = dim // 2
-    freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32, device=t.device) / half)
-    arg = t.float()[..., None] * freqs
-    return torch.cat([arg.cos(), arg.sin()] if flip_sin_to_cos else [arg.sin(), arg.cos()], dim=-1)
-
-
 class _AttnSlot(nn.Module):
     """the parameters of one cross-attention position (diffusers Attention attribute names)"""
 
@@ -507,14 +372,8 @@ class SDXLShapedUNet(nn.Module):
     def __init__(self, stage_layers=(4, 20, 10, 30, 6), cross_attention_dim=2048, ip_tokens=4, ip_scale=1.0, dtype=torch.float16, seed=0,
                  self_attention=False):
         super().__init__()
-
-        class _C:
-            in_channels = 4
-            sample_size = 128
-            time_cond_proj_dim = None
-            addition_time_embed_dim = 256
-        self.config = _C()
-        self.config.cross_attention_dim = cross_attention_dim
+        self.config = SimpleNamespace(in_channels=4, sample_size=128, time_cond_proj_dim=None, addition_time_embed_dim=256,
+                                      cross_attention_dim=cross_attention_dim)
         self.dtype_ = dtype
         self.ip_tokens, self.ip_scale = ip_tokens, ip_scale
         self.stage_layers = tuple(stage_layers)
@@ -565,36 +424,21 @@ class SDXLShapedUNet(nn.Module):
     def precompute(self, encoder_hidden_states, image_embeds=None):
         text = encoder_hidden_states.to(self.dtype_).contiguous()
         ip = self.image_tokens(image_embeds) if image_embeds is not None else None
-        B = text.shape[0]
-        kv = []
-        for s in self.slots:
-            k, v = linear16(text, s.to_k), linear16(text, s.to_v)
-            kip = vip = None
-            if ip is not None:
-                kip, vip = linear16(ip, s.to_k_ip), linear16(ip, s.to_v_ip)
-            kv.append((k, v, kip, vip))
-        # (the entry keeps the token tensors themselves: identity, not data_ptr(), decides a hit -- an address can be recycled by the allocator)
-        self._kv = (encoder_hidden_states, encoder_hidden_states._version, image_embeds, None if image_embeds is None else image_embeds._version, B, kv)
+        # (the batch is part of the hit rule: the K / V rows are per sample)
+        self._kv = TokenKV.project(encoder_hidden_states, image_embeds, text.shape[0], text, ip,
+                                   [(s.to_k, s.to_v, s.to_k_ip, s.to_v_ip) for s in self.slots])
         return self
 
     def _kv_for(self, encoder_hidden_states, image_embeds):
-        c = self._kv
-        if c is None or c[0] is not encoder_hidden_states or c[1] != encoder_hidden_states._version or c[2] is not image_embeds or \
-                c[3] != (None if image_embeds is None else image_embeds._version) or c[4] != encoder_hidden_states.shape[0]:
+        if self._kv is None or not self._kv.hit(encoder_hidden_states, image_embeds, encoder_hidden_states.shape[0]):
             self.precompute(encoder_hidden_states, image_embeds)
-        return self._kv[5]
+        return self._kv.entries
 
     # ---- forward
     def embedding(self, timestep, B, added_cond_kwargs):
-        dev = self.device
-        t = torch.as_tensor(timestep, device=dev).reshape(-1).float().expand(B)
-        temb = _sinusoid(t, 320).to(self.dtype_)
-        e = linear16(torch.nn.functional.silu(linear16(temb, self.time_w1)), self.time_w2)
-        text_embeds = added_cond_kwargs["text_embeds"].to(device=dev, dtype=self.dtype_)
-        time_ids = added_cond_kwargs["time_ids"].to(device=dev)
-        aug = torch.cat([text_embeds, _sinusoid(time_ids.flatten(), 256).reshape(B, -1).to(self.dtype_)], dim=-1)          # (B, 1280 + 6 * 256)
-        e = e + linear16(torch.nn.functional.silu(linear16(aug, self.add_w1)), self.add_w2)
-        return torch.nn.functional.silu(e)
+        """diffusers: time_embedding(320 -> 1280) + add_embedding(2816 -> 1280), without biases here"""
+        return text_time_embedding(timestep, B, added_cond_kwargs, (self.time_w1, None, self.time_w2, None), (self.add_w1, None, self.add_w2, None),
+                                   320, 256, self.dtype_, self.device)
 
     def forward(self, sample, timestep, encoder_hidden_states=None, timestep_cond=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                 return_dict=False, **kw):
@@ -602,12 +446,7 @@ class SDXLShapedUNet(nn.Module):
         B, Cc, L, _ = sample.shape
         if Cc != 4 or L % 4:
             raise EegclipError("latents must be (B, 4, L, L) with L a multiple of 4")
-        image_embeds = (added_cond_kwargs or {}).get("image_embeds")
-        if isinstance(image_embeds, (list, tuple)):
-            image_embeds = image_embeds[0]
-        if image_embeds is not None and image_embeds.dim() == 3:
-            image_embeds = image_embeds[:, 0]
-        kv = self._kv_for(encoder_hidden_states, image_embeds)
+        kv = self._kv_for(encoder_hidden_states, image_embeds_of(added_cond_kwargs))
         emb = self.embedding(timestep, B, added_cond_kwargs)                                # (B, 1280), SiLU applied
         l1, l2 = L // 2, L // 4
         # latents -> 2 x 2 patches -> (B, l1^2, 16 -> 64 zero padded)

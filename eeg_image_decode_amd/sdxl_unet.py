@@ -19,18 +19,20 @@ unet_2d_blocks.py, resnet.py, transformer_2d.py, attention.py, embeddings.py); t
           to_k_ip.0 / to_v_ip.0 (no bias) in every attn2 processor.
 
 Arithmetic (no library GEMM, no eager fallback): 16-bit padded NHWC frames between the convolutional layers (vae._FrameOps: csrc/vae.hip conv16 with the
-time-embedding add in conv1's epilogue, groupnorm16), token rows inside the transformers (csrc/gemm16.hip linear16 with fused residuals, csrc/unet.hip
+time-embedding add in conv1's epilogue, groupnorm16), token rows inside the transformers (the wrappers of ops16.py: csrc/gemm16.hip linear16 with fused residuals, csrc/unet.hip
 layernorm16 / geglu16, csrc/self_attn.hip, csrc/cross_attn.hip), skip concatenation by csrc/unet.hip concat16.  The 17 time_emb_proj layers run as ONE
 GEMM over their stacked weights; text / IP keys and values of all attn2 layers are projected once per sampling run (precompute).  The nn.Conv2d /
 nn.Linear / nn.GroupNorm / nn.LayerNorm children hold parameters only; they are never called.
 """
+from types import SimpleNamespace
+
 import torch
 import torch.nn as nn
 
-from . import _abi
-from ._lib import EegclipError, check, lib, raw_stream, require_cuda
-from .sdxl import _sinusoid, cross_attention, linear16, self_attention
-from .vae import _FrameOps, _dt
+from ._lib import EegclipError, require_cuda
+from .ops16 import (PackedWeights, TokenKV, concat16, cross_attention, geglu16, image_embeds_of, layernorm16, linear, linear16, seeded_parameters,
+                    self_attention, text_time_embedding)
+from .vae import _FrameOps
 
 RES_EPS, TF_GN_EPS, LN_EPS = 1e-5, 1e-6, 1e-5
 
@@ -130,10 +132,6 @@ class _MultiIPAdapterImageProjection(nn.Module):
         self.image_projection_layers = nn.ModuleList([_ImageProjection(image_dim, cross, tokens)])
 
 
-class _Config:
-    pass
-
-
 class SDXLUNet(_FrameOps):
     """UNet2DConditionModel in SDXL's layout (see the module docstring), state_dict keys and shapes of diffusers 0.30.0.  The default arguments are SDXL's
     config (1,680 tensors, 2,567,463,684 parameters); ip_adapter=True adds the ip-adapter_sdxl_vit-h parameters (1,824 / 2,916,651,780).  Weights get
@@ -149,13 +147,11 @@ class SDXLUNet(_FrameOps):
         chans = tuple(int(c) for c in block_out_channels)
         if any(c % 64 for c in chans):
             raise EegclipError(f"SDXLUNet: block_out_channels must be multiples of 64 (head dim 64); got {chans}")
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise EegclipError("SDXLUNet runs in fp16 or bf16")
         n = len(chans)
         tl = tuple(transformer_layers_per_block) if isinstance(transformer_layers_per_block, (tuple, list)) else (int(transformer_layers_per_block),) * n
         if len(down_block_types) != n or len(up_block_types) != n or len(tl) != n:
             raise EegclipError("SDXLUNet: one down block, one up block and one transformer depth per entry of block_out_channels")
-        cfg = self.config = _Config()
+        cfg = self.config = SimpleNamespace()
         cfg.in_channels, cfg.out_channels, cfg.sample_size = in_channels, out_channels, sample_size
         cfg.time_cond_proj_dim, cfg.addition_time_embed_dim, cfg.cross_attention_dim = None, addition_time_embed_dim, cross_attention_dim
         cfg.block_out_channels, cfg.layers_per_block, cfg.transformer_layers_per_block = chans, layers_per_block, tl
@@ -165,10 +161,7 @@ class SDXLUNet(_FrameOps):
         self.ip_adapter, self.ip_tokens, self.ip_scale = bool(ip_adapter), ip_tokens, float(ip_scale)
         temb = 4 * chans[0]
         G, eps, X = norm_num_groups, norm_eps, cross_attention_dim
-        dev = torch.device(device) if device is not None else torch.device("cpu")
-        rng_devs = [dev.index if dev.index is not None else torch.cuda.current_device()] if dev.type == "cuda" else []
-        with torch.random.fork_rng(devices=rng_devs), dev:
-            torch.manual_seed(seed)
+        with seeded_parameters(self, dtype, device, seed):
             self.conv_in = nn.Conv2d(in_channels, chans[0], 3, padding=1)
             self.time_embedding = _TimestepEmbedding(chans[0], temb)
             self.add_embedding = _TimestepEmbedding(projection_class_embeddings_input_dim, temb)
@@ -208,11 +201,8 @@ class SDXLUNet(_FrameOps):
             self.conv_out = nn.Conv2d(chans[0], out_channels, 3, padding=1)
             if self.ip_adapter:                          # (load_ip_adapter attaches it last)
                 self.encoder_hid_proj = _MultiIPAdapterImageProjection(image_embed_dim, X, ip_tokens)
-        self.to(dtype)
-        for p in self.parameters():
-            p.requires_grad_(False)
         self._init_frames()
-        self._cache, self._kv = {}, None
+        self._cache, self._kv = PackedWeights(), None
 
     def forward(self, sample, timestep, encoder_hidden_states=None, timestep_cond=None, cross_attention_kwargs=None, added_cond_kwargs=None,
                 return_dict=False, **kw):
@@ -226,14 +216,7 @@ class SDXLUNet(_FrameOps):
     def device(self):
         return self.conv_in.weight.device
 
-    # ---- packed weights: keyed on the parameters' identity, version and address (load_state_dict / in-place edits / .data swaps repack) ---------------
-    def _packed_of(self, tag, params, make):
-        key = tuple((id(p), p._version, p.data_ptr()) for p in params)
-        hit = self._cache.get(tag)
-        if hit is None or hit[0] != key:
-            hit = self._cache[tag] = (key, params, make())            # (holds the parameters: their ids cannot be recycled while the entry lives)
-        return hit[2]
-
+    # ---- packed weights: repacked when their parameters change (ops16.PackedWeights) ---------------------------------------------------------------
     def _resnets(self):
         return [r for b in self.down_blocks for r in b.resnets] + list(self.mid_block.resnets) + [r for b in self.up_blocks for r in b.resnets]
 
@@ -247,48 +230,19 @@ class SDXLUNet(_FrameOps):
             b = torch.cat([r.time_emb_proj.bias.detach() for r in rs], 0)
             pad = -w.shape[0] % 128
             return torch.nn.functional.pad(w, (0, 0, 0, pad)).contiguous(), torch.nn.functional.pad(b, (0, pad)).contiguous()
-        return self._packed_of("temb", ps, make)
+        return self._cache.get("temb", ps, make)
 
     def _qkv(self, attn):
         ps = [attn.to_q.weight, attn.to_k.weight, attn.to_v.weight]
-        return self._packed_of(("qkv", id(attn)), ps, lambda: torch.cat([p.detach() for p in ps], 0).contiguous())
+        return self._cache.get(("qkv", id(attn)), ps, lambda: torch.cat([p.detach() for p in ps], 0).contiguous())
 
     # ---- token-row layers -------------------------------------------------------------------------------------------------------------------------
     def _lin(self, x, mod, residual=None):
-        """x (M, K) rows -> (M, N) = x W^T + b (+ residual): gemm16 when N % 128 == 0, else conv16 as a 1 x 1 convolution over M pixels (Cout % 64)"""
-        N = mod.weight.shape[0]
-        if N % 128 == 0:
-            return linear16(x, mod.weight, mod.bias, residual)
-        M, K = x.shape
-        x = x.contiguous()
-        out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-        w = mod.weight.detach()
-        r = residual.contiguous() if residual is not None else None
-        d = _abi.Conv16Desc(in_=x.data_ptr(), W=w.data_ptr(), out=out.data_ptr(), bias=mod.bias.data_ptr() if mod.bias is not None else None,
-                            residual=r.data_ptr() if r is not None else None, N=1, Hi=M, Wi=1, Cin=K, in_pad=0, Ho=M, Wo=1, Cout=N, out_pad=0, KS=1, stride=1,
-                            pad_top=0, pad_left=0, upsample=0, dtype=_dt(self.dtype))
-        check(lib().eegclip_conv16(d, raw_stream()), "conv16 (1 x 1 linear)")
-        return out
-
-    def _ln(self, x, mod):
-        M, C = x.shape
-        y = torch.empty_like(x)
-        check(lib().eegclip_layernorm16(x.data_ptr(), x.stride(0), mod.weight.data_ptr(), mod.bias.data_ptr(), y.data_ptr(), C, M, C, float(mod.eps),
-                                        _dt(self.dtype), raw_stream()), "layernorm16")
-        return y
-
-    def _geglu(self, f):
-        M, D2 = f.shape
-        y = torch.empty(M, D2 // 2, dtype=f.dtype, device=f.device)
-        check(lib().eegclip_geglu16(f.data_ptr(), y.data_ptr(), M, D2 // 2, _dt(self.dtype), raw_stream()), "geglu16")
-        return y
+        return linear(x, mod.weight, mod.bias, residual)
 
     def _concat(self, a, b):
         N, Hp, Wp, Ca = a.shape
-        Cb = b.shape[3]
-        out = self._frame(N, Hp - 2, Wp - 2, Ca + Cb, 1)
-        check(lib().eegclip_concat16(a.data_ptr(), b.data_ptr(), out.data_ptr(), N, Hp - 2, Wp - 2, 1, Ca, Cb, 1, _dt(self.dtype), raw_stream()), "concat16")
-        return out
+        return concat16(a, b, self._frame(N, Hp - 2, Wp - 2, Ca + b.shape[3], 1))
 
     # ---- once per sampling run: image tokens, keys / values of every attn2 ------------------------------------------------------------------------
     def _transformers(self):
@@ -305,7 +259,7 @@ class SDXLUNet(_FrameOps):
         pr = self.encoder_hid_proj.image_projection_layers[0]
         x = linear16(image_embeds.to(self.dtype).reshape(-1, pr.image_embeds.weight.shape[1]).contiguous(), pr.image_embeds.weight, pr.image_embeds.bias)
         rows = x.reshape(-1, self.config.cross_attention_dim)
-        return self._ln(rows, pr.norm).reshape(x.shape[0], self.ip_tokens, -1)
+        return layernorm16(rows, pr.norm.weight, pr.norm.bias, pr.norm.eps).reshape(x.shape[0], self.ip_tokens, -1)
 
     def _kv_weights_key(self):
         ps = [p for a in self._attn2s() for p in (a.to_k.weight, a.to_v.weight)]
@@ -313,46 +267,24 @@ class SDXLUNet(_FrameOps):
             ps += [p for a in self._attn2s() for p in (a.processor.to_k_ip[0].weight, a.processor.to_v_ip[0].weight)]
             pr = self.encoder_hid_proj.image_projection_layers[0]
             ps += [pr.image_embeds.weight, pr.image_embeds.bias, pr.norm.weight, pr.norm.bias]
-        return tuple((id(p), p._version, p.data_ptr()) for p in ps)
+        return PackedWeights.key(ps)
 
     def precompute(self, encoder_hidden_states, image_embeds=None):
         """K / V of the text tokens (and of the 4 IP tokens) for all attn2 layers, computed once and reused by every forward with the same tensors"""
         require_cuda(encoder_hidden_states, "encoder_hidden_states")
         text = encoder_hidden_states.to(self.dtype).contiguous()
         ip = self.image_tokens(image_embeds) if image_embeds is not None else None
-        B, S, X = text.shape
-        kv = []
-        for a in self._attn2s():
-            k, v = linear16(text, a.to_k.weight), linear16(text, a.to_v.weight)
-            kip = vip = None
-            if ip is not None:
-                kip, vip = linear16(ip, a.processor.to_k_ip[0].weight), linear16(ip, a.processor.to_v_ip[0].weight)
-            kv.append((k, v, kip, vip))
-        self._kv = (encoder_hidden_states, encoder_hidden_states._version, image_embeds, None if image_embeds is None else image_embeds._version,
-                    self._kv_weights_key(), kv)
+        weights = [(a.to_k.weight, a.to_v.weight) + ((a.processor.to_k_ip[0].weight, a.processor.to_v_ip[0].weight) if ip is not None else (None, None))
+                   for a in self._attn2s()]
+        self._kv = TokenKV.project(encoder_hidden_states, image_embeds, self._kv_weights_key(), text, ip, weights)
         return self
 
     def _kv_for(self, ehs, image_embeds):
-        c = self._kv
-        if c is None or c[0] is not ehs or c[1] != ehs._version or c[2] is not image_embeds or \
-                c[3] != (None if image_embeds is None else image_embeds._version) or c[4] != self._kv_weights_key():
+        if self._kv is None or not self._kv.hit(ehs, image_embeds, self._kv_weights_key()):
             self.precompute(ehs, image_embeds)
-        return iter(self._kv[5])
+        return iter(self._kv.entries)
 
     # ---- blocks -----------------------------------------------------------------------------------------------------------------------------------
-    def _resnet(self, x, r, tb):
-        h = self._gn(x, 1, r.norm1)
-        h2 = self._conv(h, 1, r.conv1, chan_bias=tb)
-        self._done(h)
-        h = self._gn(h2, 1, r.norm2)
-        self._done(h2)
-        sc = self._conv(x, 1, r.conv_shortcut, KS=1) if hasattr(r, "conv_shortcut") else x
-        out = self._conv(h, 1, r.conv2, residual=sc)
-        self._done(h)
-        if sc is not x:
-            self._done(sc)
-        return out
-
     def _transformer(self, x, t, kv):
         N, H, W, C = x.shape[0], x.shape[1] - 2, x.shape[2] - 2, x.shape[3]
         hn = self._gn(x, 1, t.norm, silu=False, out_pad=0)
@@ -361,38 +293,28 @@ class SDXLUNet(_FrameOps):
         T = H * W
         for blk in t.transformer_blocks:
             a1, a2 = blk.attn1, blk.attn2
-            n1 = self._ln(h, blk.norm1)
+            n1 = layernorm16(h, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps)
             qkv = linear16(n1, self._qkv(a1)).reshape(N, T, 3 * C)
             o = self_attention(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], a1.heads)
             h = self._lin(o.reshape(-1, C), a1.to_out[0], h)
-            n2 = self._ln(h, blk.norm2)
+            n2 = layernorm16(h, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
             k, v, kip, vip = next(kv)
             if k.shape[0] != N:
                 raise EegclipError(f"encoder_hidden_states has batch {k.shape[0]}, sample has {N}")
             q = self._lin(n2, a2.to_q).reshape(N, T, C)
             o = cross_attention(q, k, v, a2.heads, kip, vip, self.ip_scale)
             h = self._lin(o.reshape(-1, C), a2.to_out[0], h)
-            n3 = self._ln(h, blk.norm3)
-            g = self._geglu(self._lin(n3, blk.ff.net[0].proj))
+            n3 = layernorm16(h, blk.norm3.weight, blk.norm3.bias, blk.norm3.eps)
+            g = geglu16(self._lin(n3, blk.ff.net[0].proj))
             h = self._lin(g, blk.ff.net[2], h)
         # proj_out + the block's residual, straight back into a padded frame (a 1 x 1 conv16 with residual=)
         return self._conv(h.reshape(N, H, W, C), 0, t.proj_out, out_pad=1, residual=x, KS=1)
 
     def _embedding(self, timestep, B, added):
-        """emb = time_embedding(Timesteps(C0)(t)) + add_embedding(cat(text_embeds, Timesteps(256)(time_ids))) -> silu(emb) (what every time_emb_proj reads)"""
-        if added is None or "text_embeds" not in added or "time_ids" not in added:
-            raise EegclipError("SDXLUNet needs added_cond_kwargs with 'text_embeds' and 'time_ids' (addition_embed_type 'text_time')")
-        dev, dt, c0 = self.device, self.dtype, self.config.block_out_channels[0]
-        t = torch.as_tensor(timestep, device=dev).reshape(-1).float().expand(B)
         te, ae = self.time_embedding, self.add_embedding
-        e = linear16(torch.nn.functional.silu(linear16(_sinusoid(t, c0).to(dt), te.linear_1.weight, te.linear_1.bias)), te.linear_2.weight, te.linear_2.bias)
-        text_embeds = added["text_embeds"].to(device=dev, dtype=dt)
-        time_ids = added["time_ids"].to(device=dev)
-        aug = torch.cat([text_embeds, _sinusoid(time_ids.flatten(), self.config.addition_time_embed_dim).reshape(B, -1).to(dt)], dim=-1)
-        if aug.shape[1] != ae.linear_1.weight.shape[1]:
-            raise EegclipError(f"text_embeds + time_ids give {aug.shape[1]} features; add_embedding takes {ae.linear_1.weight.shape[1]}")
-        e = e + linear16(torch.nn.functional.silu(linear16(aug.contiguous(), ae.linear_1.weight, ae.linear_1.bias)), ae.linear_2.weight, ae.linear_2.bias)
-        return torch.nn.functional.silu(e)
+        return text_time_embedding(timestep, B, added, (te.linear_1.weight, te.linear_1.bias, te.linear_2.weight, te.linear_2.bias),
+                                   (ae.linear_1.weight, ae.linear_1.bias, ae.linear_2.weight, ae.linear_2.bias), self.config.block_out_channels[0],
+                                   self.config.addition_time_embed_dim, self.dtype, self.device)
 
     @torch.no_grad()
     def _run(self, sample, timestep, ehs, added):
@@ -403,11 +325,7 @@ class SDXLUNet(_FrameOps):
             raise EegclipError(f"sample must be (B, {self.config.in_channels}, H, W) with H, W multiples of {2 ** (n - 1)}; got {tuple(sample.shape)}")
         if ehs is None:
             raise EegclipError("SDXLUNet needs encoder_hidden_states")
-        image_embeds = (added or {}).get("image_embeds")
-        if isinstance(image_embeds, (list, tuple)):
-            image_embeds = image_embeds[0]
-        if image_embeds is not None and image_embeds.dim() == 3:
-            image_embeds = image_embeds[:, 0]
+        image_embeds = image_embeds_of(added)
         if image_embeds is not None and not self.ip_adapter:
             raise EegclipError("image_embeds given to SDXLUNet(ip_adapter=False)")
         kv = self._kv_for(ehs, image_embeds)

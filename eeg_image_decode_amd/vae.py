@@ -20,16 +20,9 @@ import torch.nn as nn
 
 from . import _abi
 from ._lib import EegclipError, check, lib, raw_stream, require_cuda
+from .ops16 import PackedWeights, dtype_code, seeded_parameters
 
 GROUPS, EPS = 32, 1e-6
-
-
-def _dt(dtype):
-    if dtype == torch.bfloat16:
-        return _abi.DT_BF16
-    if dtype == torch.float16:
-        return _abi.DT_F16
-    raise EegclipError("the VAE kernels run in bf16 or fp16")
 
 
 class _Resnet(nn.Module):
@@ -100,18 +93,14 @@ class _FrameOps(nn.Module):
     NHWC frames (borders zero, never written), and the conv16 / groupnorm16 launches over them.  Subclasses call _init_frames() and define .dtype / .device."""
 
     def _init_frames(self):
-        self._packed, self._pool, self._sums = {}, {}, None
+        self._packed, self._pool, self._sums = PackedWeights(), {}, None
 
     def _w(self, mod):
         """the layer's weight as [Cout][KS * KS][Cin] (what csrc/vae.hip contracts over), packed once per parameter version"""
-        w = mod.weight
-        key = (id(w), w._version, w.data_ptr())
-        hit = self._packed.get(id(mod))
-        if hit is None or hit[0] != key:
-            p = w.detach()
-            p = (p.permute(0, 2, 3, 1).reshape(p.shape[0], -1, p.shape[1]) if p.dim() == 4 else p.reshape(p.shape[0], 1, p.shape[1])).contiguous()
-            hit = self._packed[id(mod)] = (key, p)
-        return hit[1]
+        def make():
+            p = mod.weight.detach()
+            return (p.permute(0, 2, 3, 1).reshape(p.shape[0], -1, p.shape[1]) if p.dim() == 4 else p.reshape(p.shape[0], 1, p.shape[1])).contiguous()
+        return self._packed.get(id(mod), (mod.weight,), make)
 
     def _frame(self, N, H, W, C, pad):
         """a (N, H + 2 pad, W + 2 pad, C) tensor whose border is zero: borders are never written by the kernels, so frames are recycled without clearing"""
@@ -141,7 +130,7 @@ class _FrameOps(nn.Module):
         out = self._frame(N, Ho, Wo, Cout, out_pad)
         d = _abi.Conv16Desc(in_=x.data_ptr(), W=w.data_ptr(), out=out.data_ptr(), bias=mod.bias.data_ptr() if mod.bias is not None else None,
                             residual=residual.data_ptr() if residual is not None else None, N=N, Hi=Hi, Wi=Wi, Cin=Cin, in_pad=xpad, Ho=Ho, Wo=Wo, Cout=Cout,
-                            out_pad=out_pad, KS=KS, stride=stride, pad_top=pt, pad_left=pleft, upsample=int(upsample), dtype=_dt(self.dtype),
+                            out_pad=out_pad, KS=KS, stride=stride, pad_top=pt, pad_left=pleft, upsample=int(upsample), dtype=dtype_code(self.dtype),
                             chan_bias=chan_bias.data_ptr() if chan_bias is not None else None)
         check(lib().eegclip_conv16(d, raw_stream()), "conv16")
         return out
@@ -153,7 +142,7 @@ class _FrameOps(nn.Module):
             self._sums = torch.empty(N * G * 2, dtype=torch.float64, device=self.device)
         y = self._frame(N, H, W, C, out_pad)
         check(lib().eegclip_groupnorm16(x.data_ptr(), N, H, W, C, xpad, G, mod.weight.data_ptr(), mod.bias.data_ptr(), float(mod.eps), int(silu),
-                                        y.data_ptr(), out_pad, self._sums.data_ptr(), _dt(self.dtype), raw_stream()), "groupnorm16")
+                                        y.data_ptr(), out_pad, self._sums.data_ptr(), dtype_code(self.dtype), raw_stream()), "groupnorm16")
         return y
 
     def _to_frame(self, t):
@@ -163,22 +152,32 @@ class _FrameOps(nn.Module):
         f[:, 1:-1, 1:-1, :] = t.permute(0, 2, 3, 1)
         return f
 
+    def _resnet(self, x, r, chan_bias=None):
+        """diffusers ResnetBlock2D over a padded frame; chan_bias: (N, Cout) time_emb_proj(silu(emb)), added after conv1 (the UNet's)"""
+        h = self._gn(x, 1, r.norm1)
+        h2 = self._conv(h, 1, r.conv1, chan_bias=chan_bias)
+        self._done(h)
+        h = self._gn(h2, 1, r.norm2)
+        self._done(h2)
+        sc = self._conv(x, 1, r.conv_shortcut, KS=1) if hasattr(r, "conv_shortcut") else x
+        out = self._conv(h, 1, r.conv2, residual=sc)
+        self._done(h)
+        if sc is not x:
+            self._done(sc)
+        return out
+
 
 class SDXLShapedVAE(_FrameOps):
     def __init__(self, block_out_channels=(128, 256, 512, 512), layers_per_block=2, latent_channels=4, scaling_factor=0.13025, dtype=torch.bfloat16,
                  seed=0):
         super().__init__()
-        with torch.random.fork_rng(devices=[]):
-            torch.manual_seed(seed)
+        with seeded_parameters(self, dtype, seed=seed):
             self.encoder = _Encoder(block_out_channels, layers_per_block, latent_channels)
             self.decoder = _Decoder(block_out_channels, layers_per_block, latent_channels)
             self.quant_conv = nn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
             self.post_quant_conv = nn.Conv2d(latent_channels, latent_channels, 1)
         self.latent_channels, self.scaling_factor = latent_channels, scaling_factor
         self.downscale = 2 ** (len(block_out_channels) - 1)
-        self.to(dtype)
-        for p in self.parameters():
-            p.requires_grad_(False)
         self._init_frames()
 
     def forward(self, *a, **k):
@@ -192,27 +191,14 @@ class SDXLShapedVAE(_FrameOps):
     def device(self):
         return self.post_quant_conv.weight.device
 
-    # ---- blocks (diffusers ResnetBlock2D / Attention / UNetMidBlock2D with one attention, as AutoencoderKL configures them) -------------------------
-    def _resnet(self, x, r):
-        h = self._gn(x, 1, r.norm1)
-        h2 = self._conv(h, 1, r.conv1)
-        self._done(h)
-        h = self._gn(h2, 1, r.norm2)
-        self._done(h2)
-        sc = self._conv(x, 1, r.conv_shortcut, KS=1) if hasattr(r, "conv_shortcut") else x
-        out = self._conv(h, 1, r.conv2, residual=sc)
-        self._done(h)
-        if sc is not x:
-            self._done(sc)
-        return out
-
+    # ---- blocks (diffusers Attention / UNetMidBlock2D with one attention, as AutoencoderKL configures them) -------------------------
     def _attention(self, x, a):
         """single-head self-attention over the H W positions (head dim = C), residual connection; x: padded frame"""
         N, H, W, C = x.shape[0], x.shape[1] - 2, x.shape[2] - 2, x.shape[3]
         T = H * W
         if T % 128 or C % 128:
             raise EegclipError(f"the mid-block attention takes H * W and C multiples of 128 (got {T}, {C})")
-        L, st, dt = lib(), raw_stream(), _dt(self.dtype)
+        L, st, dt = lib(), raw_stream(), dtype_code(self.dtype)
         hn = self._gn(x, 1, a.group_norm, silu=False, out_pad=0)              # (N, H, W, C) = tokens (N, T, C)
         q = self._conv(hn, 0, a.to_q, out_pad=0, KS=1)
         k = self._conv(hn, 0, a.to_k, out_pad=0, KS=1)
@@ -310,7 +296,7 @@ class SDXLShapedVAE(_FrameOps):
         if sample:
             noise = torch.randn((N, Lc, h, w), generator=generator, device=mom.device, dtype=mom.dtype).permute(0, 2, 3, 1).contiguous()
         z = torch.empty(N, h, w, Lc, dtype=mom.dtype, device=mom.device)
-        check(lib().eegclip_vae_sample16(mom.data_ptr(), noise.data_ptr() if noise is not None else None, z.data_ptr(), N * h * w, Lc, _dt(self.dtype),
+        check(lib().eegclip_vae_sample16(mom.data_ptr(), noise.data_ptr() if noise is not None else None, z.data_ptr(), N * h * w, Lc, dtype_code(self.dtype),
                                          raw_stream()), "vae_sample16")
         self._done(mom)
         return z.permute(0, 3, 1, 2).contiguous()
