@@ -124,7 +124,7 @@ class PlanOp(C.Structure):
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_GRAD = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3 = 0, 1
-ABI_VERSION = 14
+ABI_VERSION = 15
 DT_BF16, DT_F16 = 0, 1
 _P, _I, _F, _L, _U64, _U, _D = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_ulonglong, C.c_uint, C.c_double
 
@@ -227,6 +227,8 @@ PROTOTYPES = {
     "eegclip_groupnorm16": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _I, _P, _I, _P, _I, _P],
     "eegclip_softmax_rows16": [_P, _I, _I, _L, _F, _I, _P],
     "eegclip_vae_sample16": [_P, _P, _P, _L, _I, _I, _P],
+    "eegclip_vae_attn_supported": [_I, _L, _L, _L, _L],
+    "eegclip_vae_attn_fwd": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _F, _I, _P],
     "eegclip_layernorm16": [_P, _L, _P, _P, _P, _L, _I, _I, _F, _I, _P],
     "eegclip_geglu16": [_P, _P, _I, _I, _I, _P],
     "eegclip_concat16": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],

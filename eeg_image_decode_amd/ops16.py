@@ -1,7 +1,7 @@
 """The 16-bit host layer of the generation stack: what sdxl.py (processors, stand-in UNet), sdxl_unet.py, clip_text.py and vae.py share.
 
 * thin wrappers over the 16-bit entry points, free functions taking tensors: linear16 / linear (csrc/gemm16.hip, csrc/vae.hip conv16 as a 1 x 1
-  convolution), self_attention (csrc/self_attn.hip), cross_attention (csrc/cross_attn.hip), layernorm16 / geglu16 / concat16 (csrc/unet.hip),
+  convolution), self_attention (csrc/self_attn.hip), vae_attention (csrc/vae_attn.hip), cross_attention (csrc/cross_attn.hip), layernorm16 / geglu16 / concat16 (csrc/unet.hip),
   act16 / gather_rows16 (csrc/clip_text.hip).  No library GEMM, no eager fallback: a shape a kernel does not take raises.
 * PackedWeights: the one cache of repacked weights and the one statement of its key.
 * seeded_parameters: the construction of a module whose nn children hold parameters only and are never called.
@@ -106,7 +106,7 @@ def _row_layout(t, name):
     ld = t.stride(1) if T > 1 else (t.stride(0) if B > 1 else C)
     if t.stride(2) != 1 or (B > 1 and t.stride(0) != T * ld) or ld < C or ld % 8 or t.data_ptr() % 16:
         if name == "out":
-            raise EegclipError("self_attention: `out` must be (B, T, C) rows with unit column stride, a row stride that is a multiple of 8 and a "
+            raise EegclipError("attention: `out` must be (B, T, C) rows with unit column stride, a row stride that is a multiple of 8 and a "
                                "16-byte aligned base")
         t = t.contiguous()
         ld = C
@@ -145,6 +145,35 @@ def self_attention(q, k, v, heads, scale=None, out=None, causal=False):
     fwd = lib().eegclip_self_attn_causal_fwd if causal else lib().eegclip_self_attn_fwd
     check(fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, B, Tq, Tk, heads, 64, scale, _CODES[q.dtype], raw_stream()),
           "self_attn_causal_fwd" if causal else "self_attn_fwd")
+    return out
+
+
+def vae_attention(q, k, v, scale=None, out=None):
+    """softmax(scale * q k^T) v with ONE head of head_dim = C in {128, 256, 384, 512} (flash-style, csrc/vae_attn.hip: no T x T buffer; the VAE's
+    mid-block attention).  q, k, v (B, T, C), fp16 or bf16, any T >= 1; the three may be column slices of one packed (B, T, 3C) projection (consumed
+    in place).  scale defaults to 1 / sqrt(C).  Returns `out` (B, T, C), which may be given."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        require_cuda(t, n)
+    if q.dtype not in _CODES or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise EegclipError(f"vae_attention runs in fp16 or bf16 with one dtype for q, k, v (got {q.dtype}, {k.dtype}, {v.dtype})")
+    if q.dim() != 3 or tuple(k.shape) != tuple(q.shape) or tuple(v.shape) != tuple(q.shape):
+        raise EegclipError(f"vae_attention takes three (B, T, C) tensors of one shape (got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)})")
+    B, T, C = q.shape
+    if C % 128 or not 128 <= C <= 512:
+        raise EegclipError(f"vae_attention: head_dim must be 128, 256, 384 or 512 (got {C})")
+    if B * T == 0:
+        raise EegclipError("vae_attention: empty input")
+    q, ldq = _row_layout(q, "q")
+    k, ldk = _row_layout(k, "k")
+    v, ldv = _row_layout(v, "v")
+    if out is None:
+        out = torch.empty(B, T, C, dtype=q.dtype, device=q.device)
+    elif tuple(out.shape) != (B, T, C) or out.dtype != q.dtype or out.device != q.device:
+        raise EegclipError(f"vae_attention: out {tuple(out.shape)} {out.dtype} does not match ({B}, {T}, {C}) {q.dtype}")
+    out, ldo = _row_layout(out, "out")
+    scale = 1.0 / math.sqrt(C) if scale is None else float(scale)
+    check(lib().eegclip_vae_attn_fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, B, T, C, scale, _CODES[q.dtype],
+                                     raw_stream()), "vae_attn_fwd")
     return out
 
 

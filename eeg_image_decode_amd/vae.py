@@ -9,8 +9,9 @@ so that a real checkpoint loads with `load_state_dict`; offline its weights are 
 architecture (oracle/sdxl_vae.py, fp32 torch; "parity unpinned" like every diffusers row of SURVEY.md section 8c).
 
 Arithmetic: csrc/vae.hip -- 16-bit padded-NHWC activations, fp32 accumulation; 3 x 3 / 1 x 1 convolutions as implicit GEMMs on the matrix cores (nearest-2x
-upsampling and stride-2 downsampling folded into the row addressing), GroupNorm + SiLU as one statistics and one apply pass, the mid-block attention as
-three eegclip_gemm16 launches around a row softmax.  The nn.Conv2d / nn.GroupNorm / nn.Linear children hold parameters only; they are never called.
+upsampling and stride-2 downsampling folded into the row addressing), GroupNorm + SiLU as one statistics and one apply pass; the mid-block attention is
+one packed q | k | v projection and one flash-style launch over all images (csrc/vae_attn.hip: any H x W, no T x T buffer).  The nn.Conv2d /
+nn.GroupNorm / nn.Linear children hold parameters only; they are never called.
 bf16 by default: the reference upcasts its fp16 VAE to fp32 for the decode because fp16 overflows there (custom_pipeline.py:412-419); bf16 has fp32's range.
 """
 import math
@@ -20,7 +21,7 @@ import torch.nn as nn
 
 from . import _abi
 from ._lib import EegclipError, check, lib, raw_stream, require_cuda
-from .ops16 import PackedWeights, dtype_code, seeded_parameters
+from .ops16 import PackedWeights, dtype_code, seeded_parameters, vae_attention
 
 GROUPS, EPS = 32, 1e-6
 
@@ -119,8 +120,11 @@ class _FrameOps(nn.Module):
     def _conv(self, x, xpad, mod, out_pad=1, stride=1, pads=None, upsample=False, residual=None, KS=None, chan_bias=None):
         """x: (N, Hi + 2 xpad, Wi + 2 xpad, Cin) frame -> (N, Ho + 2 out_pad, Wo + 2 out_pad, Cout) frame.  pads = (top, left, bottom, right) zero padding of
         the convolution (default: "same"); upsample: over the nearest-2x upsampled input; chan_bias: (N, Cout) added per image and channel"""
+        return self._conv_wb(x, xpad, self._w(mod), mod.bias, out_pad, stride, pads, upsample, residual, KS, chan_bias)
+
+    def _conv_wb(self, x, xpad, w, bias, out_pad=1, stride=1, pads=None, upsample=False, residual=None, KS=None, chan_bias=None):
+        """_conv with the packed weight [Cout][KS * KS][Cin] and the bias (or None) given as tensors"""
         N, Hi, Wi, Cin = x.shape[0], x.shape[1] - 2 * xpad, x.shape[2] - 2 * xpad, x.shape[3]
-        w = self._w(mod)
         Cout, KS = w.shape[0], (KS or int(round(math.sqrt(w.shape[1]))))
         pt, pleft, pb, pr = pads if pads is not None else ((KS - 1) // 2,) * 4
         if upsample:
@@ -128,7 +132,7 @@ class _FrameOps(nn.Module):
         else:
             Ho, Wo = (Hi + pt + pb - KS) // stride + 1, (Wi + pleft + pr - KS) // stride + 1
         out = self._frame(N, Ho, Wo, Cout, out_pad)
-        d = _abi.Conv16Desc(in_=x.data_ptr(), W=w.data_ptr(), out=out.data_ptr(), bias=mod.bias.data_ptr() if mod.bias is not None else None,
+        d = _abi.Conv16Desc(in_=x.data_ptr(), W=w.data_ptr(), out=out.data_ptr(), bias=bias.data_ptr() if bias is not None else None,
                             residual=residual.data_ptr() if residual is not None else None, N=N, Hi=Hi, Wi=Wi, Cin=Cin, in_pad=xpad, Ho=Ho, Wo=Wo, Cout=Cout,
                             out_pad=out_pad, KS=KS, stride=stride, pad_top=pt, pad_left=pleft, upsample=int(upsample), dtype=dtype_code(self.dtype),
                             chan_bias=chan_bias.data_ptr() if chan_bias is not None else None)
@@ -194,6 +198,27 @@ class SDXLShapedVAE(_FrameOps):
     # ---- blocks (diffusers Attention / UNetMidBlock2D with one attention, as AutoencoderKL configures them) -------------------------
     def _attention(self, x, a):
         """single-head self-attention over the H W positions (head dim = C), residual connection; x: padded frame"""
+        N, H, W, C = x.shape[0], x.shape[1] - 2, x.shape[2] - 2, x.shape[3]
+        T = H * W
+        if C % 128 or C > 512:
+            # csrc/vae_attn.hip holds a query's C output columns in registers, 512 at the most; no other kernel serves a wider head, so wider VAEs
+            # (none of the reference's) keep the T x T form below with its H * W % 128 == 0 rule
+            return self._attention_wide(x, a)
+        hn = self._gn(x, 1, a.group_norm, silu=False, out_pad=0)              # (N, H, W, C) = tokens (N, T, C)
+        lin = (a.to_q, a.to_k, a.to_v)
+        params = tuple(m.weight for m in lin) + tuple(m.bias for m in lin)
+        w, b = self._packed.get(("qkv", id(a)), params, lambda: (torch.cat([m.weight.detach() for m in lin]).reshape(3 * C, 1, C).contiguous(),
+                                                                 torch.cat([m.bias.detach() for m in lin])))
+        qkv = self._conv_wb(hn, 0, w, b, out_pad=0, KS=1)                      # (N, H, W, 3C) = [q | k | v], consumed in place
+        o = self._frame(N, H, W, C, 0)
+        tok = qkv.view(N, T, 3 * C)
+        vae_attention(tok[..., :C], tok[..., C:2 * C], tok[..., 2 * C:], out=o.view(N, T, C))
+        out = self._conv(o, 0, a.to_out[0], out_pad=1, residual=x, KS=1)
+        self._done(hn, qkv, o)
+        return out
+
+    def _attention_wide(self, x, a):
+        """_attention for C > 512 (or C % 128): gemm16 launches around a row softmax over a T x T score matrix, one image at a time"""
         N, H, W, C = x.shape[0], x.shape[1] - 2, x.shape[2] - 2, x.shape[3]
         T = H * W
         if T % 128 or C % 128:

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 14
+#define EEGCLIP_ABI_VERSION 15
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -640,6 +640,17 @@ int eegclip_groupnorm16(const void* x, int N, int H, int W, int C, int pad, int 
                         int out_pad, double* sums, int dtype, void* stream);
 int eegclip_softmax_rows16(void* s, int rows, int cols, long long ld, float scale, int dtype, void* stream);
 int eegclip_vae_sample16(const void* moments, const void* noise, void* z, long long pixels, int latent_channels, int dtype, void* stream);
+
+/* ---- the VAE's mid-block attention as one flash-style launch (csrc/vae_attn.hip; Generation/custom_pipeline.py:421 `vae.decode`,
+ * Generation/custom_pipeline_low_level.py:8-31 `vae.encode`: diffusers' Attention with a single head over the H W positions, head_dim = C):
+ *   out[b, i, :] = sum_j softmax_j(scale * q[b,i] . k[b,j]) v[b,j]      i, j < T;  q / k / v / out are (B * T, ld) rows, sample b's rows from b * T * ld
+ * head_dim 128, 256, 384 or 512 (SDXL's VAE: 512); strides in elements, so a packed (B * T, 3 C) projection is consumed in place.  16-bit I/O (dtype), fp32
+ * scores / softmax / accumulation, probabilities rounded to the I/O dtype before P V; no T x T buffer.  Any T >= 1, B <= 65535, scale > 0 and finite.  Writes
+ * only rows < T, columns [0, head_dim) of out.  Strides multiples of 8 and >= head_dim, pointers 16-byte aligned; _supported() checks head_dim and strides
+ * alone.  (ABI 15.) */
+int eegclip_vae_attn_supported(int head_dim, long long ldq, long long ldk, long long ldv, long long ldo);
+int eegclip_vae_attn_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B, int T,
+                         int head_dim, float scale, int dtype, void* stream);
 
 /* ---- the SDXL UNet's remaining layers (csrc/unet.hip; Generation/custom_pipeline.py:456-492 loads UNet2DConditionModel from stabilityai/sdxl-turbo, diffusers
  * 0.30.0 attention.py BasicTransformerBlock / GEGLU, unet_2d_blocks.py skip concatenation), 16-bit in and out, fp32 arithmetic:
