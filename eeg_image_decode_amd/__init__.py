@@ -6,3 +6,14 @@ C-ABI in include/eegclip.h; there is NO CPU fallback: importing the compute modu
 without the built library (or calling them without a GPU) raises.
 """
 __version__ = "0.1.0"
+
+# the caption decoder's public names, resolved on first use: importing the package itself stays free of torch (build.py imports it before the library exists)
+_LAZY = {"GITCaptioner": "git_caption", "WordPieceDecoder": "git_caption", "caption": "git_caption"}
+__all__ = sorted(_LAZY)
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        import importlib
+        return getattr(importlib.import_module("." + _LAZY[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -124,7 +124,7 @@ class PlanOp(C.Structure):
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_GRAD = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3 = 0, 1
-ABI_VERSION = 15
+ABI_VERSION = 16
 DT_BF16, DT_F16 = 0, 1
 _P, _I, _F, _L, _U64, _U, _D = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_ulonglong, C.c_uint, C.c_double
 
@@ -190,6 +190,9 @@ PROTOTYPES = {
     "eegclip_self_attn_supported": [_I, _L, _L, _L, _L],
     "eegclip_self_attn_fwd": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P],
     "eegclip_self_attn_causal_fwd": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P],
+    "eegclip_self_attn_prefix_fwd": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P],
+    "eegclip_gemm16_skinny": [_P, _L, _P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _P],
+    "eegclip_decode_attn16": [_P, _L, _P, _L, _L, _P, _L, _I, _I, _I, _I, _F, _I, _P],
     "eegclip_sconv_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
     "eegclip_sconv_fwd_workspace_floats": [_I],
     "eegclip_sconv_bwd_w_workspace_floats": [_I, _I],

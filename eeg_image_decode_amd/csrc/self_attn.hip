@@ -23,6 +23,10 @@
 // query.  Key 0 is visible to every query, so the running maximum is still finite from the first tile on; a tile that is wholly masked for one
 // query (the second tile of a 128-query workgroup, for its first 64 queries) leaves that query's m, l and accumulators as they were
 // (exp2(-inf) = 0, alpha = exp2(0) = 1).  The non-causal instantiations compile to the code they had without the flag.
+// PREFIX-CAUSAL (GIT's caption decoder, eeg_image_decode_amd/git_caption.py: `prefix` image tokens in front of the text): the causal instantiation with a
+// runtime bound, key j reaches query i iff j < max(i + 1, prefix) -- the image tokens see each other, everything after them is causal.  prefix = 0 is the
+// causal form, bit for bit (the same instructions on the same operands).  A workgroup's key loop ends at max(its last query + 1, prefix) and only the
+// tiles that reach past max(its first query + 1, prefix) are masked.
 #include "attn16.h"
 
 namespace eeg {
@@ -41,6 +45,7 @@ struct sa_args {
     long long ldq, ldk, ldv, ldo;
     int Tq, Tk;
     float scale2;   // scale * log2(e)
+    int prefix;     // CAUSAL only: keys < prefix are visible to every query (0: plain causal)
 };
 
 // ds_read_b64_tr_b16: per 16-lane group, lane 4q+p addresses row q, columns 4p..4p+3 of a 4 x 16 block; lane i receives column i, row q in
@@ -101,7 +106,8 @@ __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
     int nkt = (a.Tk + SA_KT - 1) / SA_KT;
     if (CAUSAL) {                                                          // stop after the tile of the workgroup's last query (Tq == Tk)
         const int qend = (int)(blockIdx.x + 1) * (64 * QT), qlast = (qend < a.Tq ? qend : a.Tq) - 1;
-        if (qlast / SA_KT + 1 < nkt) nkt = qlast / SA_KT + 1;
+        const int klast = qlast + 1 > a.prefix ? qlast : a.prefix - 1;         // the last key any query of the workgroup sees
+        if (klast / SA_KT + 1 < nkt) nkt = klast / SA_KT + 1;
     }
 
     sa_stage st;
@@ -150,14 +156,16 @@ __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
                     for (int p = 0; p < QT; ++p) s[p][t][r] = in ? s[p][t][r] : -INFINITY;
                 }
         }
-        if (CAUSAL && kt * SA_KT + SA_KT - 1 > (int)blockIdx.x * (64 * QT)) {   // the tile reaches past the workgroup's first query: keys > query -> -inf
+        const int q0 = (int)blockIdx.x * (64 * QT);
+        if (CAUSAL && kt * SA_KT + SA_KT - 1 > (q0 + 1 > a.prefix ? q0 : a.prefix - 1)) {   // the tile reaches past what the workgroup's first query sees
 #pragma unroll
             for (int p = 0; p < QT; ++p) {
                 const int qrow = blockIdx.x * (64 * QT) + (p * 4 + wave) * 16 + fr;
+                const int lim = qrow + 1 > a.prefix ? qrow + 1 : a.prefix;   // keys < lim are visible
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) s[p][t][r] = kt * SA_KT + 16 * t + 4 * g + r <= qrow ? s[p][t][r] : -INFINITY;
+                    for (int r = 0; r < 4; ++r) s[p][t][r] = kt * SA_KT + 16 * t + 4 * g + r < lim ? s[p][t][r] : -INFINITY;
             }
         }
         bf16x8 pa[QT][2];
@@ -238,18 +246,18 @@ extern "C" int eegclip_self_attn_supported(int head_dim, long long ldq, long lon
     return 0;
 }
 
-static int sa_forward(bool causal, const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B, int Tq,
+static int sa_forward(bool causal, int prefix, const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B, int Tq,
                       int Tk, int heads, int head_dim, float scale, int dtype, void* stream) {
     const int rc = eegclip_self_attn_supported(head_dim, ldq, ldk, ldv, ldo);
     if (rc) return rc;
     if (!q || !k || !v || !out || B < 1 || Tq < 1 || Tk < 1 || heads < 1 || B > 65535 || heads > 65535 || !(scale > 0.f) || !(scale < INFINITY)) return EEGCLIP_EINVAL;
-    if (causal && Tq != Tk) return EEGCLIP_EINVAL;
+    if (causal && (Tq != Tk || prefix < 0 || prefix > Tk)) return EEGCLIP_EINVAL;
     if (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16) return EEGCLIP_EINVAL;
     const long long C = (long long)heads * SA_D;
     if (ldq < C || ldk < C || ldv < C || ldo < C) return EEGCLIP_EINVAL;
     if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) != 0) return EEGCLIP_EALIGN;
     const sa_args a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (unsigned short*)out, ldq, ldk, ldv, ldo, Tq, Tk,
-                    scale * 1.44269504088896340736f};
+                    scale * 1.44269504088896340736f, prefix};
     const size_t lds = sizeof(unsigned short) * 4 * SA_TILE;                // 40 KB: two (K, V) tile buffers
     // 128 queries per workgroup, or 64 when that leaves fewer than two workgroups per CU (256 CUs): SDXL's 1024-token stage at one image is
     // 160 workgroups of 128
@@ -279,10 +287,15 @@ static int sa_forward(bool causal, const void* q, long long ldq, const void* k, 
 
 extern "C" int eegclip_self_attn_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo,
                                      int B, int Tq, int Tk, int heads, int head_dim, float scale, int dtype, void* stream) {
-    return sa_forward(false, q, ldq, k, ldk, v, ldv, out, ldo, B, Tq, Tk, heads, head_dim, scale, dtype, stream);
+    return sa_forward(false, 0, q, ldq, k, ldk, v, ldv, out, ldo, B, Tq, Tk, heads, head_dim, scale, dtype, stream);
 }
 
 extern "C" int eegclip_self_attn_causal_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo,
                                             int B, int Tq, int Tk, int heads, int head_dim, float scale, int dtype, void* stream) {
-    return sa_forward(true, q, ldq, k, ldk, v, ldv, out, ldo, B, Tq, Tk, heads, head_dim, scale, dtype, stream);
+    return sa_forward(true, 0, q, ldq, k, ldk, v, ldv, out, ldo, B, Tq, Tk, heads, head_dim, scale, dtype, stream);
+}
+
+extern "C" int eegclip_self_attn_prefix_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo,
+                                            int B, int T, int prefix, int heads, int head_dim, float scale, int dtype, void* stream) {
+    return sa_forward(true, prefix, q, ldq, k, ldk, v, ldv, out, ldo, B, T, T, heads, head_dim, scale, dtype, stream);
 }

@@ -1,7 +1,7 @@
 """The 16-bit host layer of the generation stack: what sdxl.py (processors, stand-in UNet), sdxl_unet.py, clip_text.py and vae.py share.
 
 * thin wrappers over the 16-bit entry points, free functions taking tensors: linear16 / linear (csrc/gemm16.hip, csrc/vae.hip conv16 as a 1 x 1
-  convolution), self_attention (csrc/self_attn.hip), vae_attention (csrc/vae_attn.hip), cross_attention (csrc/cross_attn.hip), layernorm16 / geglu16 / concat16 (csrc/unet.hip),
+  convolution), linear16_skinny / decode_attention (csrc/caption.hip), self_attention (csrc/self_attn.hip), vae_attention (csrc/vae_attn.hip), cross_attention (csrc/cross_attn.hip), layernorm16 / geglu16 / concat16 (csrc/unet.hip),
   act16 / gather_rows16 (csrc/clip_text.hip).  No library GEMM, no eager fallback: a shape a kernel does not take raises.
 * PackedWeights: the one cache of repacked weights and the one statement of its key.
 * seeded_parameters: the construction of a module whose nn children hold parameters only and are never called.
@@ -113,10 +113,15 @@ def _row_layout(t, name):
     return t, ld
 
 
-def self_attention(q, k, v, heads, scale=None, out=None, causal=False):
+def self_attention(q, k, v, heads, scale=None, out=None, causal=False, prefix=None):
     """softmax(scale * q k^T) v per head of 64 (flash-style, csrc/self_attn.hip: no T x T buffer).  q (B, Tq, C), k / v (B, Tk, C), C = heads * 64,
     fp16 or bf16; the three may be column slices of one fused (B, T, 3C) projection (consumed in place).  scale defaults to 1/8 (diffusers'
-    attn.scale).  causal: key j reaches query i only if j <= i (CLIP's text encoders; Tq == Tk).  Returns `out` (B, Tq, C), which may be given."""
+    attn.scale).  causal: key j reaches query i only if j <= i (CLIP's text encoders; Tq == Tk).  prefix (an int in [0, T]; Tq == Tk): key j reaches
+    query i iff j < max(i + 1, prefix) (GIT's caption decoder: `prefix` image tokens ahead of causal text).  Returns `out` (B, Tq, C), which may be given."""
+    if prefix is not None:
+        if causal:
+            raise EegclipError("self_attention: give `causal` or `prefix`, not both (prefix=0 is the causal mask)")
+        causal = True
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         require_cuda(t, n)
     if q.dtype not in _CODES or k.dtype != q.dtype or v.dtype != q.dtype:
@@ -142,9 +147,74 @@ def self_attention(q, k, v, heads, scale=None, out=None, causal=False):
         raise EegclipError(f"self_attention: out {tuple(out.shape)} {out.dtype} does not match ({B}, {Tq}, {C}) {q.dtype}")
     out, ldo = _row_layout(out, "out")
     scale = 1.0 / math.sqrt(64) if scale is None else float(scale)
+    if prefix is not None:
+        if not 0 <= int(prefix) <= Tk:
+            raise EegclipError(f"self_attention: prefix must be in [0, {Tk}]; got {prefix}")
+        check(lib().eegclip_self_attn_prefix_fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, B, Tq, int(prefix), heads, 64, scale,
+                                                 _CODES[q.dtype], raw_stream()), "self_attn_prefix_fwd")
+        return out
     fwd = lib().eegclip_self_attn_causal_fwd if causal else lib().eegclip_self_attn_fwd
     check(fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, B, Tq, Tk, heads, 64, scale, _CODES[q.dtype], raw_stream()),
           "self_attn_causal_fwd" if causal else "self_attn_fwd")
+    return out
+
+
+def decode_attention(q, cache, Tk, heads, scale=None):
+    """one query row per sample against the first Tk rows of a key / value cache (csrc/caption.hip decode_attn16): q (B, C) -- a column slice of a (B, 3C)
+    projection qualifies --, cache (B, Tmax, 2C) rows [k | v], C = heads * 64; every key is visible.  Returns (B, C)."""
+    require_cuda(q, "q")
+    require_cuda(cache, "cache")
+    dt = dtype_code(q)
+    C = heads * 64
+    if q.dim() != 2 or q.shape[1] != C or cache.dim() != 3 or cache.shape[0] != q.shape[0] or cache.shape[2] != 2 * C or cache.dtype != q.dtype:
+        raise EegclipError(f"decode_attention: q {tuple(q.shape)} {q.dtype} / cache {tuple(cache.shape)} {cache.dtype} are not (B, {C}) / (B, Tmax, {2 * C})")
+    B, Tmax = q.shape[0], cache.shape[1]
+    if not 1 <= Tk <= Tmax:
+        raise EegclipError(f"decode_attention: Tk must be in [1, {Tmax}]; got {Tk}")
+    if q.stride(1) != 1 or cache.stride(2) != 1:
+        raise EegclipError("decode_attention: q and cache must have unit column stride")
+    out = torch.empty(B, C, dtype=q.dtype, device=q.device)
+    scale = 1.0 / math.sqrt(64) if scale is None else float(scale)
+    check(lib().eegclip_decode_attn16(q.data_ptr(), q.stride(0) if B > 1 else max(q.stride(0), C), cache.data_ptr(), cache.stride(1),
+                                      cache.stride(0) if B > 1 else max(cache.stride(0), Tk * cache.stride(1)), out.data_ptr(), C, B, int(Tk), heads, 64, scale, dt,
+                                      raw_stream()), "decode_attn16")
+    return out
+
+
+def linear16_skinny(x, weight, bias=None, residual=None, out=None, out_f32=False):
+    """y = x @ weight.T (+ bias) (+ residual) for few rows (csrc/caption.hip gemm16_skinny: the weight is streamed once; 16 rows per launch, more rows
+    take one launch per 16).  x (M, K), weight (N, K) with any N, K % 64 == 0; residual (M, N); `out` (M, N) may be given as a view with any row
+    stride (a cache row per sample); out_f32: fp32 output (the LM head's logits)."""
+    require_cuda(x, "x")
+    dt = dtype_code(x)
+    if x.dim() != 2 or weight.dim() != 2 or weight.shape[1] != x.shape[1] or weight.dtype != x.dtype:
+        raise EegclipError(f"linear16_skinny: weight {tuple(weight.shape)} {weight.dtype} does not match input {tuple(x.shape)} {x.dtype}")
+    M, K = x.shape
+    N = weight.shape[0]
+    if K % 64 or M < 1:
+        raise EegclipError(f"linear16_skinny takes K % 64 == 0 and at least one row (got M = {M}, K = {K})")
+    if x.stride(1) != 1 or x.stride(0) % 8:
+        x = x.contiguous()
+    w = weight if weight.is_contiguous() else weight.contiguous()
+    odt = torch.float32 if out_f32 else x.dtype
+    if out is None:
+        out = torch.empty(M, N, dtype=odt, device=x.device)
+    elif tuple(out.shape) != (M, N) or out.dtype != odt or out.stride(1) != 1 or out.device != x.device:
+        raise EegclipError(f"linear16_skinny: out {tuple(out.shape)} {out.dtype} is not ({M}, {N}) {odt} rows with unit column stride")
+    r = None
+    if residual is not None:
+        r = residual if residual.stride(1) == 1 else residual.contiguous()
+        if tuple(r.shape) != (M, N) or r.dtype != x.dtype:
+            raise EegclipError("linear16_skinny: residual does not match the output")
+    if bias is not None and (bias.dtype != x.dtype or bias.numel() != N):
+        raise EegclipError("linear16_skinny: bias does not match the output")
+    b = bias.contiguous() if bias is not None else None
+    ldc = out.stride(0) if M > 1 else max(out.stride(0), N)
+    for m0 in range(0, M, 16):
+        mm = min(16, M - m0)
+        check(lib().eegclip_gemm16_skinny(x.data_ptr() + 2 * m0 * x.stride(0), max(x.stride(0), K), w.data_ptr(), K, out.data_ptr() + out.element_size() * m0 * ldc,
+                                          ldc, b.data_ptr() if b is not None else None, r.data_ptr() + 2 * m0 * r.stride(0) if r is not None else None,
+                                          max(r.stride(0), N) if r is not None else 0, mm, N, K, int(out_f32), dt, raw_stream()), "gemm16_skinny")
     return out
 
 

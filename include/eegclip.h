@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 15
+#define EEGCLIP_ABI_VERSION 16
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -446,6 +446,12 @@ int eegclip_self_attn_fwd(const void* q, long long ldq, const void* k, long long
  * and requirements, and Tq == Tk (anything else: EEGCLIP_EINVAL).  Key tiles past a workgroup's last query are neither loaded nor multiplied. */
 int eegclip_self_attn_causal_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B,
                                  int Tq, int Tk, int heads, int head_dim, float scale, int dtype, void* stream);
+/* the prefix-causal form (GIT's caption decoder, Generation/modeling_git.py:1970-1973 hands `prefix` visual tokens in ahead of the text; the mask is
+ * transformers' GitModel's): key j contributes to query i iff j <= i or (i < prefix and j < prefix), i.e. j < max(i + 1, prefix); T rows of queries and of
+ * keys.  0 <= prefix <= T (anything else: EEGCLIP_EINVAL); prefix = 0 computes eegclip_self_attn_causal_fwd bit for bit, prefix = T the unmasked
+ * attention.  Otherwise the causal form's arguments and requirements.  A workgroup's key loop ends at max(its last query + 1, prefix). */
+int eegclip_self_attn_prefix_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B,
+                                 int T, int prefix, int heads, int head_dim, float scale, int dtype, void* stream);
 
 /* ---- retrieval readouts.  ATMS_retrieval.py:246 (argmax), :320 (top-5).  ties -> lowest index; out_idx: int64 (rows, k), k <= 8 */
 int eegclip_topk_rows(const float* X, int rows, int cols, long long ld, int k, const float* scale /* device scalar or NULL: rank by scale*x */,
@@ -675,6 +681,25 @@ int eegclip_concat16(const void* a, const void* b, void* out, int N, int H, int 
 int eegclip_gather_rows16(const void* table, long long table_rows, const void* idx, int idx64, const void* add, int add_rows, void* out, int rows, int C,
                           int dtype, void* stream);
 int eegclip_act16(const void* x, long long ldx, void* y, long long ldy, int M, int D, int kind, int dtype, void* stream);
+
+/* ---- the GIT caption decoder's per-token kernels (csrc/caption.hip; Generation/modeling_git.py: GitForCausalLMClipEmb = transformers' GitForCausalLM with the
+ * visual tokens handed in, :1970-1973), 16-bit in (dtype), fp32 arithmetic.  Its prefill runs on eegclip_gemm16, eegclip_layernorm16, eegclip_act16,
+ * eegclip_gather_rows16 and eegclip_self_attn_prefix_fwd; its greedy choice is eegclip_topk_rows (k = 1).
+ *   eegclip_gemm16_skinny  C[m][n] = sum_k A[m][k] W[n][k] (+ bias[n]) (+ R[m][n]) for 1 <= M <= 16 (more: EEGCLIP_EINVAL), K % 64 == 0, any N >= 1: the Linear
+ *                          layers of one decoding step (M = the batch), W (N, K) in nn.Linear's layout read once with 16-byte loads, K split over the waves
+ *                          of a workgroup and summed in LDS in a fixed order (bit-reproducible; no atomics, no workspace).  A, W 16-byte aligned with row
+ *                          strides lda, ldw multiples of 8; bias (N) and R (M rows, stride ldr) of `dtype`, either may be NULL; C of `dtype` (c_f32 = 0) or
+ *                          fp32 (c_f32 = 1: the LM head's logits), row stride ldc >= N in elements of C -- with ldc = Tmax * 2C the k | v projection of a
+ *                          new token lands in each sample's cache row.
+ *   eegclip_decode_attn16  out[b, 64h .. 64h+63] = sum_j softmax_j(scale * q[b,h] . k[b,j,h]) v[b,j,h], j < Tk: one query row per sample (row b at q + b * ldq;
+ *                          the q part of a (B, 3C) or (B, C) buffer), keys and values the first Tk rows of a cache whose row j of sample b is
+ *                          kv + b * sample_stride + j * ld_row = [k (C) | v (C)], C = heads * 64.  Every key is visible (the newest token is the last
+ *                          row); rows >= Tk are never read; no score buffer.  head_dim 64, Tk >= 1, scale > 0, ld_row >= 2C, sample_stride >= Tk * ld_row,
+ *                          strides multiples of 8, pointers 16-byte aligned.  Writes out[b * ldo + 0 .. C) only. */
+int eegclip_gemm16_skinny(const void* A, long long lda, const void* W, long long ldw, void* C, long long ldc, const void* bias, const void* R, long long ldr,
+                          int M, int N, int K, int c_f32, int dtype, void* stream);
+int eegclip_decode_attn16(const void* q, long long ldq, const void* kv, long long ld_row, long long sample_stride, void* out, long long ldo, int B, int Tk,
+                          int heads, int head_dim, float scale, int dtype, void* stream);
 
 /* ---- the projection head's GEMMs at M = the batch (csrc/head_gemm.hip; Retrieval/ATMS_retrieval.py:157-167 forward, its input gradients, and the query
  * gradient of the loss, models/loss.py:122-140): C[m][n] = sum_k A[m][k] B[n][k] from k-contiguous bf16 hi | lo planes like eegclip_gemm_planes, but
