@@ -85,6 +85,12 @@ class Conv16Desc(C.Structure):
                 ("chan_bias", C.c_void_p)]
 
 
+class Convt16Desc(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("W", C.c_void_p), ("out", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
+                ("N", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int), ("Cin", C.c_int), ("Ho", C.c_int), ("Wo", C.c_int), ("Cout", C.c_int),
+                ("KS", C.c_int), ("stride", C.c_int), ("pad", C.c_int), ("relu", C.c_int), ("tap_mask", C.c_int), ("dtype", C.c_int)]
+
+
 class WgradTokProblem(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("a_group_stride", C.c_longlong), ("m_groups", C.c_int), ("heads_m", C.c_int), ("heads_n", C.c_int),
                 ("M", C.c_int), ("N", C.c_int), ("out", C.c_void_p), ("ldo", C.c_longlong), ("bias_out", C.c_void_p), ("bias_mfma", C.c_int),
@@ -124,7 +130,7 @@ class PlanOp(C.Structure):
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_GRAD = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3 = 0, 1
-ABI_VERSION = 16
+ABI_VERSION = 17
 DT_BF16, DT_F16 = 0, 1
 _P, _I, _F, _L, _U64, _U, _D = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_ulonglong, C.c_uint, C.c_double
 
@@ -193,6 +199,7 @@ PROTOTYPES = {
     "eegclip_self_attn_prefix_fwd": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P],
     "eegclip_gemm16_skinny": [_P, _L, _P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     "eegclip_decode_attn16": [_P, _L, _P, _L, _L, _P, _L, _I, _I, _I, _I, _F, _I, _P],
+    "eegclip_convt16": [C.POINTER(Convt16Desc), _P],
     "eegclip_sconv_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
     "eegclip_sconv_fwd_workspace_floats": [_I],
     "eegclip_sconv_bwd_w_workspace_floats": [_I, _I],

@@ -2,7 +2,7 @@
 
 * thin wrappers over the 16-bit entry points, free functions taking tensors: linear16 / linear (csrc/gemm16.hip, csrc/vae.hip conv16 as a 1 x 1
   convolution), linear16_skinny / decode_attention (csrc/caption.hip), self_attention (csrc/self_attn.hip), vae_attention (csrc/vae_attn.hip), cross_attention (csrc/cross_attn.hip), layernorm16 / geglu16 / concat16 (csrc/unet.hip),
-  act16 / gather_rows16 (csrc/clip_text.hip).  No library GEMM, no eager fallback: a shape a kernel does not take raises.
+  act16 / gather_rows16 (csrc/clip_text.hip), conv_transpose16 (csrc/convt16.hip).  No library GEMM, no eager fallback: a shape a kernel does not take raises.
 * PackedWeights: the one cache of repacked weights and the one statement of its key.
 * seeded_parameters: the construction of a module whose nn children hold parameters only and are never called.
 * what both UNets do around their attention stacks: image_embeds_of, text_time_embedding, TokenKV.
@@ -284,6 +284,54 @@ def concat16(a, b, out):
     """padded NHWC frames a (N, H + 2, W + 2, Ca), b (.., Cb) -> the caller's frame `out` (.., Ca + Cb): the skip concatenation"""
     N, Hp, Wp, Ca = a.shape
     check(lib().eegclip_concat16(a.data_ptr(), b.data_ptr(), out.data_ptr(), N, Hp - 2, Wp - 2, 1, Ca, b.shape[3], 1, dtype_code(a), raw_stream()), "concat16")
+    return out
+
+
+_CONVT_K = ((1, 3), (2, 0))     # [phase half][tap half] -> index into the 4-wide kernel along that axis (include/eegclip.h, eegclip_convt16)
+
+
+def pack_conv_transpose16(weight):
+    """nn.ConvTranspose2d(.., 4, 2, 1)'s weight (Cin, Cout, 4, 4) -> the kernel's [phase 2 py + px][Cout][tap 2 ty + tx][Cin] (K contiguous)"""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (4, 4):
+        raise EegclipError(f"pack_conv_transpose16 takes a (Cin, Cout, 4, 4) weight; got {tuple(weight.shape)}")
+    w = weight.detach()
+    return torch.stack([torch.stack([w[:, :, _CONVT_K[py][ty], _CONVT_K[px][tx]].t() for ty in (0, 1) for tx in (0, 1)], dim=1)
+                        for py in (0, 1) for px in (0, 1)], dim=0).contiguous()
+
+
+def conv_transpose_live_taps(Hi, Wi):
+    """eegclip_convt16's tap_mask without the taps whose source is in the zero border for every pixel: the neighbour row when Hi == 1, the neighbour column
+    when Wi == 1 (at 1 x 1 three of four taps, and their weights, are never read)"""
+    nib = sum(1 << t for t in range(4) if not ((t >> 1) and Hi == 1) and not ((t & 1) and Wi == 1))
+    return nib * 0x1111
+
+
+def conv_transpose16(x_frame, packed_w, scale=None, shift=None, relu=False, out=None):
+    """ConvTranspose2d(kernel 4, stride 2, padding 1) + y * scale[co] + shift[co] (+ ReLU) on csrc/convt16.hip.  x_frame: padded NHWC (N, Hi + 2, Wi + 2, Cin)
+    with a zero border; packed_w: pack_conv_transpose16's (4, Cout, 4, Cin); scale / shift: fp32 (Cout) or None (1 / 0).  Cout % 16 == 0: returns the padded
+    NHWC frame (N, 2 Hi + 2, 2 Wi + 2, Cout) of the next layer (`out`, if given, must already have a zero border: only its interior is written);
+    Cout < 16: returns unpadded NCHW (N, Cout, 2 Hi, 2 Wi)."""
+    require_cuda(x_frame, "x_frame")
+    dt = dtype_code(x_frame)
+    if x_frame.dim() != 4 or packed_w.dim() != 4 or packed_w.shape[0] != 4 or packed_w.shape[2] != 4 or packed_w.shape[3] != x_frame.shape[3] or \
+            packed_w.dtype != x_frame.dtype or min(x_frame.shape[1:3]) < 3:
+        raise EegclipError(f"conv_transpose16: frame {tuple(x_frame.shape)} {x_frame.dtype} / packed weight {tuple(packed_w.shape)} {packed_w.dtype} do not match "
+                           f"(N, Hi + 2, Wi + 2, Cin) / (4, Cout, 4, Cin)")
+    N, Hi, Wi, Cin = x_frame.shape[0], x_frame.shape[1] - 2, x_frame.shape[2] - 2, x_frame.shape[3]
+    Cout = packed_w.shape[1]
+    x_frame, packed_w = x_frame.contiguous(), packed_w.contiguous()
+    shape = (N, 2 * Hi + 2, 2 * Wi + 2, Cout) if Cout >= 16 else (N, Cout, 2 * Hi, 2 * Wi)
+    if out is None:
+        out = (torch.zeros if Cout >= 16 else torch.empty)(shape, dtype=x_frame.dtype, device=x_frame.device)
+    elif tuple(out.shape) != shape or out.dtype != x_frame.dtype or out.device != x_frame.device or not out.is_contiguous():
+        raise EegclipError(f"conv_transpose16: out {tuple(out.shape)} {out.dtype} is not a contiguous {shape} {x_frame.dtype}")
+    for v, n in ((scale, "scale"), (shift, "shift")):
+        if v is not None and (v.dtype != torch.float32 or v.numel() != Cout or not v.is_contiguous() or v.device != x_frame.device):
+            raise EegclipError(f"conv_transpose16: {n} must be a contiguous fp32 vector of {Cout} on the input's device")
+    d = _abi.Convt16Desc(in_=x_frame.data_ptr(), W=packed_w.data_ptr(), out=out.data_ptr(), scale=scale.data_ptr() if scale is not None else None,
+                         shift=shift.data_ptr() if shift is not None else None, N=N, Hi=Hi, Wi=Wi, Cin=Cin, Ho=2 * Hi, Wo=2 * Wi, Cout=Cout, KS=4, stride=2, pad=1,
+                         relu=int(bool(relu)), tap_mask=conv_transpose_live_taps(Hi, Wi), dtype=dt)
+    check(lib().eegclip_convt16(d, raw_stream()), "convt16")
     return out
 
 

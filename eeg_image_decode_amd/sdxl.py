@@ -777,16 +777,21 @@ class Generator4Embeds:
         install_cross_attention_processors(pipe.unet, scale=1.0)
         self.pipe = pipe
 
-    def generate(self, image_embeds, text_prompt='', generator=None):
+    def generate(self, image_embeds, text_prompt='', generator=None, low_level_latent=None):
+        """low_level_latent: this call's start latent (e.g. low_level.LowLevelEncoder's output for the trial) in place of the constructor's, so one generator
+        serves a batch of trials; None keeps the constructor's"""
+        low_level_latent = self.low_level_latent if low_level_latent is None else low_level_latent
         image_embeds = image_embeds.to(device=self.device, dtype=self.dtype)
         if image_embeds.dim() == 1:
             image_embeds = image_embeds[None]
         if not self._stand_in:
+            if low_level_latent is not None and low_level_latent is not self.low_level_latent:
+                raise EegclipError("Generator4Embeds.generate(low_level_latent=...) needs the stand-in pipeline's generate_ip_adapter_embeds: pass pipe=")
             return self.pipe(prompt=text_prompt, ip_adapter_image_embeds=[image_embeds.unsqueeze(1)], num_inference_steps=self.num_inference_steps,
                              guidance_scale=0.0, generator=generator).images[0]
         return self.pipe.generate_ip_adapter_embeds(prompt=text_prompt, ip_adapter_embeds=image_embeds, num_inference_steps=self.num_inference_steps,
                                                     guidance_scale=0.0, generator=generator, img2img_strength=self.img2img_strength,
-                                                    low_level_image=self.low_level_image, low_level_latent=self.low_level_latent).images[0]
+                                                    low_level_image=self.low_level_image, low_level_latent=low_level_latent).images[0]
 
 
 def bench_sampling_loop(images=8, steps=50, latent=128, guidance_scale=5.0, dtype=torch.float16, self_attention=False):

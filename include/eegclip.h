@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 16
+#define EEGCLIP_ABI_VERSION 17
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -700,6 +700,33 @@ int eegclip_gemm16_skinny(const void* A, long long lda, const void* W, long long
                           int M, int N, int K, int c_f32, int dtype, void* stream);
 int eegclip_decode_attn16(const void* q, long long ldq, const void* kv, long long ld_row, long long sample_stride, void* out, long long ldo, int B, int Tk,
                           int heads, int head_dim, float scale, int dtype, void* stream);
+
+/* ---- the transposed convolutions of the low-level EEG -> VAE-latent encoder (csrc/convt16.hip; Generation/train_vae_latent_512_low_level_no_average.py:219-260,
+ * encoder_low_level.upsampler: ConvTranspose2d(kernel 4, stride 2, padding 1) + BatchNorm2d + ReLU per layer, a bare ConvTranspose2d last).  (ABI 17.)
+ *   eegclip_convt16   out[n][2y - 1 + ky][2x - 1 + kx][co] += in[n][y][x][ci] w[ci][co][ky][kx] (torch's ConvTranspose2d), then y = acc * scale[co] + shift[co],
+ *                     ReLU if relu, one rounding to `dtype`; fp32 accumulation.  `in` is a padded NHWC frame (N, Hi + 2, Wi + 2, Cin) with a zero border, Cin % 64
+ *                     == 0.  Cout % 16 == 0: matrix-core form, `out` a padded NHWC frame (N, Ho + 2, Wo + 2, Cout) whose interior alone is written (the border
+ *                     stays as the caller zeroed it).  Cout < 16 (16 Cout Cin weights <= 64 KB): direct form, `out` UNPADDED NCHW (N, Cout, Ho, Wo).  Ho = 2 Hi,
+ *                     Wo = 2 Wi; KS, stride, pad must be 4, 2, 1 (anything else: EEGCLIP_EINVAL).
+ *                     W is the PACKED weight [phase 2 py + px][Cout][tap 2 ty + tx][Cin]: output pixel (2y + py, 2x + px) sums, per axis, tap half 0 = the
+ *                     source pixel itself (k = 1 for an even phase, k = 2 for an odd one) and tap half 1 = its neighbour (k = 3, source - 1 for an even
+ *                     phase; k = 0, source + 1 for an odd one).  tap_mask: bit 4 phase + tap set = the tap is read; 0xffff reads all.  A tap whose source is
+ *                     in the zero border for every pixel (ty = 1 when Hi == 1, tx = 1 when Wi == 1) may be cleared and its weights are then never read, with
+ *                     bit-identical results; a mask that clears any other tap, or sets bits above 15, is EEGCLIP_EINVAL.
+ *                     scale / shift: fp32 (Cout) vectors, the eval-mode BatchNorm folded with the convolution's bias; scale NULL = 1, shift NULL = 0 (a plain
+ *                     bias is shift alone).  in, W 16-byte aligned.  Bit-reproducible: K is split over the waves of a workgroup and summed in a fixed order. */
+typedef struct {
+    const void* in;
+    const void* W;
+    void* out;
+    const float* scale;
+    const float* shift;
+    int N, Hi, Wi, Cin;
+    int Ho, Wo, Cout;
+    int KS, stride, pad;
+    int relu, tap_mask, dtype;
+} eegclip_convt16_desc;
+int eegclip_convt16(const eegclip_convt16_desc* d, void* stream);
 
 /* ---- the projection head's GEMMs at M = the batch (csrc/head_gemm.hip; Retrieval/ATMS_retrieval.py:157-167 forward, its input gradients, and the query
  * gradient of the loss, models/loss.py:122-140): C[m][n] = sum_k A[m][k] B[n][k] from k-contiguous bf16 hi | lo planes like eegclip_gemm_planes, but
