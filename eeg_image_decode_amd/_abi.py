@@ -91,6 +91,29 @@ class Convt16Desc(C.Structure):
                 ("KS", C.c_int), ("stride", C.c_int), ("pad", C.c_int), ("relu", C.c_int), ("tap_mask", C.c_int), ("dtype", C.c_int)]
 
 
+class Convt16BwdDataDesc(C.Structure):
+    _fields_ = [("dz", C.c_void_p), ("W", C.c_void_p), ("dx", C.c_void_p), ("N", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
+                ("tap_mask", C.c_int), ("dtype", C.c_int)]
+
+
+class Convt16BwdWeightDesc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("dz", C.c_void_p), ("dW", C.c_void_p), ("db", C.c_void_p), ("workspace", C.c_void_p), ("workspace_floats", C.c_longlong),
+                ("N", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("slabs", C.c_int), ("loss_scale", C.c_float),
+                ("dtype", C.c_int)]
+
+
+class Bn2d16FwdDesc(C.Structure):
+    _fields_ = [("z", C.c_void_p), ("a", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p),
+                ("running_mean", C.c_void_p), ("running_var", C.c_void_p), ("workspace", C.c_void_p), ("workspace_floats", C.c_longlong), ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int),
+                ("eps", C.c_float), ("momentum", C.c_float), ("dtype", C.c_int)]
+
+
+class Bn2d16BwdDesc(C.Structure):
+    _fields_ = [("da", C.c_void_p), ("a", C.c_void_p), ("z", C.c_void_p), ("gamma", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p), ("dgamma", C.c_void_p),
+                ("dbeta", C.c_void_p), ("dz", C.c_void_p), ("workspace", C.c_void_p), ("workspace_floats", C.c_longlong), ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int),
+                ("loss_scale", C.c_float), ("dtype", C.c_int)]
+
+
 class WgradTokProblem(C.Structure):
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("a_group_stride", C.c_longlong), ("m_groups", C.c_int), ("heads_m", C.c_int), ("heads_n", C.c_int),
                 ("M", C.c_int), ("N", C.c_int), ("out", C.c_void_p), ("ldo", C.c_longlong), ("bias_out", C.c_void_p), ("bias_mfma", C.c_int),
@@ -130,7 +153,7 @@ class PlanOp(C.Structure):
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_GRAD = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3 = 0, 1
-ABI_VERSION = 17
+ABI_VERSION = 18
 DT_BF16, DT_F16 = 0, 1
 _P, _I, _F, _L, _U64, _U, _D = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_ulonglong, C.c_uint, C.c_double
 
@@ -200,6 +223,14 @@ PROTOTYPES = {
     "eegclip_gemm16_skinny": [_P, _L, _P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     "eegclip_decode_attn16": [_P, _L, _P, _L, _L, _P, _L, _I, _I, _I, _I, _F, _I, _P],
     "eegclip_convt16": [C.POINTER(Convt16Desc), _P],
+    "eegclip_convt16_pack_train": [_P, _P, _P, _I, _I, _I, _P],
+    "eegclip_convt16_bwd_data": [C.POINTER(Convt16BwdDataDesc), _P],
+    "eegclip_convt16_bwd_weight_slabs": [_I, _I, _I, _I, _I],
+    "eegclip_convt16_bwd_weight_workspace_floats": [_I, _I, _I, _I, _I, _I],
+    "eegclip_convt16_bwd_weight": [C.POINTER(Convt16BwdWeightDesc), _P],
+    "eegclip_bn2d16_workspace_floats": [_I, _I, _I, _I],
+    "eegclip_bn2d16_fwd": [C.POINTER(Bn2d16FwdDesc), _P],
+    "eegclip_bn2d16_bwd": [C.POINTER(Bn2d16BwdDesc), _P],
     "eegclip_sconv_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
     "eegclip_sconv_fwd_workspace_floats": [_I],
     "eegclip_sconv_bwd_w_workspace_floats": [_I, _I],

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 17
+#define EEGCLIP_ABI_VERSION 18
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -727,6 +727,87 @@ typedef struct {
     int relu, tap_mask, dtype;
 } eegclip_convt16_desc;
 int eegclip_convt16(const eegclip_convt16_desc* d, void* stream);
+
+/* ---- training the low-level encoder: the backward of eegclip_convt16 and train-mode BatchNorm2d + ReLU on the same frames (csrc/convt16_bwd.hip, csrc/bn2d16.hip;
+ * Generation/train_vae_latent_512_low_level_no_average.py:219-260 differentiated, an MSE regression onto VAE latents).  (ABI 18.)  z / dz = the RAW convolution
+ * output frame (N, 2 Hi + 2, 2 Wi + 2, Cout) and its gradient, x / dx the input frame (N, Hi + 2, Wi + 2, Cin); zero borders.  Cin % 64 == 0; Cout % 64 == 0
+ * (matrix-core forms, 16-bit padded NHWC dz) or Cout < 16 with 16 Cout Cin weights <= 64 KB (direct forms: dz is UNPADDED fp32 NCHW (N, Cout, 2 Hi, 2 Wi), the
+ * layout of the loss gradient).  fp32 accumulation; no atomics, fixed summation orders: bit-reproducible.
+ *   eegclip_convt16_pack_train   fp32 W (Cin, Cout, 4, 4) -> `fwd`, the packing eegclip_convt16 reads (the bits of packing the rounded weight), and `bwd`
+ *                     [Cin][4 ky + kx][Cout], what eegclip_convt16_bwd_data reads; one launch.
+ *   eegclip_convt16_bwd_data     dx[n][y][x][ci] = sum_{ky,kx,co} dz[n][2y - 1 + ky][2x - 1 + kx][co] W[ci][co][ky][kx], one rounding to `dtype`; the interior of
+ *                     dx alone is written.  tap_mask: bit 4 ky + kx set = the tap is read; 0xffff reads all.  ky in {0, 3} when Hi == 1 and kx in {0, 3} when
+ *                     Wi == 1 only meet the border of dz and may be cleared (their weights are then never read; same bits); a mask that clears any other
+ *                     tap, or sets bits above 15, is EEGCLIP_EINVAL.  dz, W 16-byte aligned.
+ *   eegclip_convt16_bwd_weight   dW[ci][co][ky][kx] = (sum_{n,y,x} x[n][y][x][ci] dz[n][2y - 1 + ky][2x - 1 + kx][co]) / loss_scale in torch's layout, fp32;
+ *                     db[co] = (sum of dz) / loss_scale (db may be NULL).  The pixels are split over `slabs` workgroup slabs that the launch's reduction adds
+ *                     in slab order (1 <= slabs <= the 32-pixel tiles, or the pixels for the direct form; eegclip_convt16_bwd_weight_slabs proposes a count);
+ *                     workspace: eegclip_convt16_bwd_weight_workspace_floats floats, 16-byte aligned.  Taps that only meet the border get exact zeros. */
+int eegclip_convt16_pack_train(const float* W, void* fwd, void* bwd, int Cin, int Cout, int dtype, void* stream);
+typedef struct {
+    const void* dz;
+    const void* W;
+    void* dx;
+    int N, Hi, Wi, Cin, Cout;
+    int tap_mask, dtype;
+} eegclip_convt16_bwd_data_desc;
+int eegclip_convt16_bwd_data(const eegclip_convt16_bwd_data_desc* d, void* stream);
+typedef struct {
+    const void* x;
+    const void* dz;
+    float* dW;
+    float* db;
+    float* workspace;
+    long long workspace_floats;
+    int N, Hi, Wi, Cin, Cout;
+    int slabs;
+    float loss_scale;
+    int dtype;
+} eegclip_convt16_bwd_weight_desc;
+int eegclip_convt16_bwd_weight_slabs(int N, int Hi, int Wi, int Cin, int Cout);
+long long eegclip_convt16_bwd_weight_workspace_floats(int N, int Hi, int Wi, int Cin, int Cout, int slabs);
+int eegclip_convt16_bwd_weight(const eegclip_convt16_bwd_weight_desc* d, void* stream);
+/*   eegclip_bn2d16_fwd   per channel over the M = N H W >= 2 interior pixels of z (N, H + 2, W + 2, C), C % 64 == 0: mean and biased variance in fp32 (fixed-order
+ *                     partial sums, added in fp64), mean / rstd = 1 / sqrt(var + eps) saved, running_mean / running_var (either may be NULL) updated with
+ *                     `momentum` and the unbiased variance as nn.BatchNorm2d does; a = relu((z - mean) rstd gamma + beta), one rounding, into the interior of
+ *                     the frame `a`.  Three launches.
+ *   eegclip_bn2d16_bwd   g = da [a > 0]; dbeta = sum g / loss_scale, dgamma = sum g xhat / loss_scale (xhat = (z - mean) rstd);
+ *                     dz = gamma rstd (g - sum g / M - xhat sum g xhat / M), one rounding, into the interior of the frame dz (still scaled).  Three launches.
+ *   workspace: eegclip_bn2d16_workspace_floats(N, H, W, C) floats for either; workspace_floats states what the caller gave, less is EEGCLIP_EINVAL. */
+typedef struct {
+    const void* z;
+    void* a;
+    const float* gamma;
+    const float* beta;
+    float* mean;
+    float* rstd;
+    float* running_mean;
+    float* running_var;
+    float* workspace;
+    long long workspace_floats;
+    int N, H, W, C;
+    float eps, momentum;
+    int dtype;
+} eegclip_bn2d16_fwd_desc;
+typedef struct {
+    const void* da;
+    const void* a;
+    const void* z;
+    const float* gamma;
+    const float* mean;
+    const float* rstd;
+    float* dgamma;
+    float* dbeta;
+    void* dz;
+    float* workspace;
+    long long workspace_floats;
+    int N, H, W, C;
+    float loss_scale;
+    int dtype;
+} eegclip_bn2d16_bwd_desc;
+long long eegclip_bn2d16_workspace_floats(int N, int H, int W, int C);
+int eegclip_bn2d16_fwd(const eegclip_bn2d16_fwd_desc* d, void* stream);
+int eegclip_bn2d16_bwd(const eegclip_bn2d16_bwd_desc* d, void* stream);
 
 /* ---- the projection head's GEMMs at M = the batch (csrc/head_gemm.hip; Retrieval/ATMS_retrieval.py:157-167 forward, its input gradients, and the query
  * gradient of the loss, models/loss.py:122-140): C[m][n] = sum_k A[m][k] B[n][k] from k-contiguous bf16 hi | lo planes like eegclip_gemm_planes, but
