@@ -36,29 +36,14 @@ struct ax_args {
     unsigned site;
 };
 
-typedef short ax_s4 __attribute__((ext_vector_type(4)));
 typedef float ax_f2 __attribute__((ext_vector_type(2)));
 typedef float ax_f4u __attribute__((ext_vector_type(4), aligned(4)));      // 16-byte global access from a dword-aligned address
 
-// LDS transpose read (see the header): 4 bf16 for this lane
-__device__ __forceinline__ ax_s4 ax_tr_read(const unsigned char* p) {
-#if defined(EEG_EMU)
-    const int lane = hipemu::cur->lane, g = lane >> 4, i = lane & 15;
-    ax_s4 r;
-    for (int j = 0; j < 4; ++j) {
-        const unsigned long long src = hipemu::shfl_idx((unsigned long long)(uintptr_t)p, 16 * g + 4 * j + (i >> 2));
-        r[j] = reinterpret_cast<const short*>((uintptr_t)src)[i & 3];
-    }
-    return r;
-#else
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ax_s4*)(p));
-#endif
-}
 // fragment with k slots 0-3 <-> rows r0 .. r0+3 and 4-7 <-> rows r1 .. r1+3 of column c0 + (lane & 15) of a [row][col] plane
 __device__ __forceinline__ bf16x8 ax_tr_frag(const unsigned char* plane, int r0, int r1, int c0, int lane) {
     const int l = lane & 15;
-    const ax_s4 a = ax_tr_read(plane + (r0 + (l >> 2)) * AX_RS + 2 * (c0 + 4 * (l & 3)));
-    const ax_s4 b = ax_tr_read(plane + (r1 + (l >> 2)) * AX_RS + 2 * (c0 + 4 * (l & 3)));
+    const s16x4 a = lds_read_tr16(plane + (r0 + (l >> 2)) * AX_RS + 2 * (c0 + 4 * (l & 3)));
+    const s16x4 b = lds_read_tr16(plane + (r1 + (l >> 2)) * AX_RS + 2 * (c0 + 4 * (l & 3)));
     return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 }
 __device__ __forceinline__ bf16x8 ax_frag(const unsigned char* plane, int row, int k0) {      // 8 consecutive k of one row

@@ -9,21 +9,11 @@
 //              UNBIASED variance, as nn.BatchNorm2d) -> bn2d_fwd_apply_kernel: a = relu((z - mean) rstd gamma + beta), one rounding, interior only.
 //   backward   bn2d_bwd_partial_kernel (sum g, sum g xhat; g = da [a > 0], xhat = (z - mean) rstd) -> bn2d_bwd_finalize_kernel (dbeta, dgamma divided by
 //              loss_scale; the scaled sums / M stay in the workspace) -> bn2d_bwd_apply_kernel: dz = gamma rstd (g - sum g / M - xhat sum g xhat / M).
-#include "attn16.h"
+#include "half16.h"
 
 #include <string.h>
 
 namespace eeg {
-
-template <bool F16>
-__device__ __forceinline__ float bn_to_f32(unsigned short u) {
-    if (F16) {
-        _Float16 h;
-        memcpy(&h, &u, 2);
-        return (float)h;
-    }
-    return bf16_bits_to_f32(u);
-}
 
 struct bn_args {
     const unsigned short *z, *a, *da;           // frames (a, da: backward only)
@@ -59,15 +49,15 @@ __global__ __launch_bounds__(256) void bn2d_partial_kernel(const bn_args a) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const unsigned short ab = (unsigned short)av[e];
-                const float g = (ab & 0x7fff) && !(ab & 0x8000) ? bn_to_f32<F16>((unsigned short)dv[e]) : 0.f;
-                const float xh = (bn_to_f32<F16>((unsigned short)zv[e]) - mu[e]) * rs[e];
+                const float g = (ab & 0x7fff) && !(ab & 0x8000) ? to_f32<F16>((unsigned short)dv[e]) : 0.f;
+                const float xh = (to_f32<F16>((unsigned short)zv[e]) - mu[e]) * rs[e];
                 s0[e] += g;
                 s1[e] += g * xh;
             }
         } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float v = bn_to_f32<F16>((unsigned short)zv[e]);
+                const float v = to_f32<F16>((unsigned short)zv[e]);
                 s0[e] += v;
                 s1[e] += v * v;
             }
@@ -139,11 +129,11 @@ __global__ __launch_bounds__(256) void bn2d_apply_kernel(const bn_args a) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int c = c0 + e;
-        const float xh = (bn_to_f32<F16>((unsigned short)zv[e]) - a.mean[c]) * a.rstd[c];
+        const float xh = (to_f32<F16>((unsigned short)zv[e]) - a.mean[c]) * a.rstd[c];
         float v;
         if (BWD) {
             const unsigned short ab = (unsigned short)av[e];
-            const float g = (ab & 0x7fff) && !(ab & 0x8000) ? bn_to_f32<F16>((unsigned short)dv[e]) : 0.f;
+            const float g = (ab & 0x7fff) && !(ab & 0x8000) ? to_f32<F16>((unsigned short)dv[e]) : 0.f;
             v = a.gamma[c] * a.rstd[c] * (g - sums[c] - xh * sums[a.C + c]);
         } else {
             v = fmaxf(xh * a.gamma[c] + a.beta[c], 0.f);
@@ -165,7 +155,7 @@ static int bn_slabs(int M, int* pix) {
 }
 
 static int bn_shape(int N, int H, int W, int C, int dtype) {
-    if (N < 1 || H < 1 || W < 1 || H > 32768 || W > 32768 || C < 64 || C % 64 || (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16)) return EEGCLIP_EINVAL;
+    if (N < 1 || H < 1 || W < 1 || H > 32768 || W > 32768 || C < 64 || C % 64 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
     const long long M = (long long)N * H * W;
     if (M < 2 || M > 0x7fffffffLL / 16) return EEGCLIP_EINVAL;              // one value per channel has no variance (nn.BatchNorm2d raises)
     return 0;

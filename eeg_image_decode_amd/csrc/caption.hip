@@ -17,21 +17,9 @@
 //     sample, every key visible.  One workgroup per (sample, head); 8 lanes hold one key row (16 bytes each), a wave takes 8 keys per step and the 4 waves
 //     interleave steps.  Each 8-lane group runs its own online softmax (running max, sum, 8 accumulator columns per lane); the groups are merged with xor
 //     shuffles and the waves in LDS.  Rows >= Tk are never read.  fp32 probabilities (no 16-bit rounding before P V here: there is no matrix core operand).
-#include "attn16.h"
+#include "half16.h"
 
 namespace eeg {
-
-typedef unsigned short cp_u16x8 __attribute__((ext_vector_type(8)));
-
-template <bool F16>
-__device__ __forceinline__ float cp_to_f32(unsigned short u) {
-    if (F16) {
-        _Float16 h;
-        memcpy(&h, &u, 2);
-        return (float)h;
-    }
-    return bf16_bits_to_f32(u);
-}
 
 struct sk_args {
     const unsigned short *A, *W, *bias, *R;
@@ -85,8 +73,8 @@ __global__ __launch_bounds__(64 * WAVES) void gemm16_skinny_kernel(const sk_args
             float v = red[t];
 #pragma unroll
             for (int w = 1; w < WAVES; ++w) v += red[w * 256 + t];
-            if (a.bias) v += cp_to_f32<F16>(a.bias[n]);
-            if (a.R) v += cp_to_f32<F16>(a.R[(long long)m * a.ldr + n]);
+            if (a.bias) v += to_f32<F16>(a.bias[n]);
+            if (a.R) v += to_f32<F16>(a.R[(long long)m * a.ldr + n]);
             if (a.c_f32) static_cast<float*>(a.C)[(long long)m * a.ldc + n] = v;
             else         static_cast<unsigned short*>(a.C)[(long long)m * a.ldc + n] = to_h<F16>(v);
         }
@@ -110,10 +98,10 @@ __global__ __launch_bounds__(256) void decode_attn16_kernel(const da_args a) {
     const long long C = (long long)a.heads * 64;
     float qf[8], acc[8];
     {
-        const cp_u16x8 qv = *reinterpret_cast<const cp_u16x8*>(a.q + (long long)b * a.ldq + h * 64 + 8 * part);
+        const u16x8 qv = *reinterpret_cast<const u16x8*>(a.q + (long long)b * a.ldq + h * 64 + 8 * part);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            qf[e] = cp_to_f32<F16>(qv[e]);
+            qf[e] = to_f32<F16>(qv[e]);
             acc[e] = 0.f;
         }
     }
@@ -122,14 +110,14 @@ __global__ __launch_bounds__(256) void decode_attn16_kernel(const da_args a) {
     for (int j0 = wave * 8; j0 < a.Tk; j0 += 32) {                          // (wave-uniform trip count)
         const int j = j0 + slot;
         const bool in = j < a.Tk;
-        cp_u16x8 kk{0, 0, 0, 0, 0, 0, 0, 0}, vv{0, 0, 0, 0, 0, 0, 0, 0};
+        u16x8 kk{0, 0, 0, 0, 0, 0, 0, 0}, vv{0, 0, 0, 0, 0, 0, 0, 0};
         if (in) {
-            kk = *reinterpret_cast<const cp_u16x8*>(kb + (long long)j * a.ld_row);
-            vv = *reinterpret_cast<const cp_u16x8*>(kb + (long long)j * a.ld_row + C);
+            kk = *reinterpret_cast<const u16x8*>(kb + (long long)j * a.ld_row);
+            vv = *reinterpret_cast<const u16x8*>(kb + (long long)j * a.ld_row + C);
         }
         float s = 0.f;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) s += qf[e] * cp_to_f32<F16>(kk[e]);
+        for (int e = 0; e < 8; ++e) s += qf[e] * to_f32<F16>(kk[e]);
         s += __shfl_xor(s, 1, 64);
         s += __shfl_xor(s, 2, 64);
         s += __shfl_xor(s, 4, 64);
@@ -139,7 +127,7 @@ __global__ __launch_bounds__(256) void decode_attn16_kernel(const da_args a) {
             const float p = fast_exp2((s - mn) * a.scale2);
             l = l * alpha + p;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] = acc[e] * alpha + p * cp_to_f32<F16>(vv[e]);
+            for (int e = 0; e < 8; ++e) acc[e] = acc[e] * alpha + p * to_f32<F16>(vv[e]);
             m = mn;
         }
     }
@@ -200,8 +188,7 @@ static void sk_launch(const sk_args& a, void* stream) {
 
 extern "C" int eegclip_gemm16_skinny(const void* A, long long lda, const void* W, long long ldw, void* C, long long ldc, const void* bias, const void* R,
                                      long long ldr, int M, int N, int K, int c_f32, int dtype, void* stream) {
-    if (!A || !W || !C || M < 1 || M > 16 || N < 1 || K < 64 || K % 64 || lda < K || ldw < K || ldc < N || (R && ldr < N) || (c_f32 != 0 && c_f32 != 1) ||
-        (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16))
+    if (!A || !W || !C || M < 1 || M > 16 || N < 1 || K < 64 || K % 64 || lda < K || ldw < K || ldc < N || (R && ldr < N) || (c_f32 != 0 && c_f32 != 1) || !half_dtype_ok(dtype))
         return EEGCLIP_EINVAL;
     if (!cp_a16(A) || !cp_a16(W) || lda % 8 || ldw % 8 || (reinterpret_cast<uintptr_t>(C) & (c_f32 ? 3u : 1u)) ||
         (bias && (reinterpret_cast<uintptr_t>(bias) & 1u)) || (R && (reinterpret_cast<uintptr_t>(R) & 1u)))
@@ -215,8 +202,7 @@ extern "C" int eegclip_gemm16_skinny(const void* A, long long lda, const void* W
 
 extern "C" int eegclip_decode_attn16(const void* q, long long ldq, const void* kv, long long ld_row, long long sample_stride, void* out, long long ldo, int B, int Tk,
                                      int heads, int head_dim, float scale, int dtype, void* stream) {
-    if (!q || !kv || !out || B < 1 || B > 65535 || Tk < 1 || heads < 1 || heads > 65535 || head_dim != 64 || !(scale > 0.f) || !(scale < INFINITY) ||
-        (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16))
+    if (!q || !kv || !out || B < 1 || B > 65535 || Tk < 1 || heads < 1 || heads > 65535 || head_dim != 64 || !(scale > 0.f) || !(scale < INFINITY) || !half_dtype_ok(dtype))
         return EEGCLIP_EINVAL;
     const long long C = (long long)heads * 64;
     if (ldq < C || ldo < C || ld_row < 2 * C || sample_stride < (long long)Tk * ld_row) return EEGCLIP_EINVAL;

@@ -6,31 +6,9 @@
 //                  it (the host module rejects such ids before the launch: the clamp keeps a stray index from being read through).
 //   act16          the MLP's activation between fc1 and fc2: kind 0 = x * sigmoid(1.702 x) (transformers' quick_gelu, the first encoder), kind 1 = the exact
 //                  erf GELU (the second encoder; the form geglu16 uses).  In place allowed.
-#include "eeg_common.h"
+#include "half16.h"
 
 namespace eeg {
-
-typedef unsigned short ct_u16x8 __attribute__((ext_vector_type(8)));
-
-template <bool F16>
-__device__ __forceinline__ float ct_to_f32(unsigned short u) {
-    if (F16) {
-        _Float16 h;
-        memcpy(&h, &u, 2);
-        return (float)h;
-    }
-    return bf16_bits_to_f32(u);
-}
-template <bool F16>
-__device__ __forceinline__ unsigned short ct_from_f32(float v) {
-    if (F16) {
-        const _Float16 h = (_Float16)v;
-        unsigned short u;
-        memcpy(&u, &h, 2);
-        return u;
-    }
-    return f32_to_bf16_bits(v);
-}
 
 template <bool F16, bool IDX64>
 __global__ __launch_bounds__(256) void gather_rows16_kernel(const unsigned short* __restrict__ table, long long table_rows, const void* __restrict__ idx,
@@ -42,13 +20,13 @@ __global__ __launch_bounds__(256) void gather_rows16_kernel(const unsigned short
         const int r = (int)(q / c8), j = 8 * (int)(q - (long long)r * c8);
         long long i = IDX64 ? static_cast<const long long*>(idx)[r] : (long long)static_cast<const int*>(idx)[r];
         i = i < 0 ? 0 : (i >= table_rows ? table_rows - 1 : i);
-        ct_u16x8 v = *reinterpret_cast<const ct_u16x8*>(table + i * C + j);
+        u16x8 v = *reinterpret_cast<const u16x8*>(table + i * C + j);
         if (add) {
-            const ct_u16x8 p = *reinterpret_cast<const ct_u16x8*>(add + (long long)(r % add_rows) * C + j);
+            const u16x8 p = *reinterpret_cast<const u16x8*>(add + (long long)(r % add_rows) * C + j);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = ct_from_f32<F16>(ct_to_f32<F16>(v[e]) + ct_to_f32<F16>(p[e]));
+            for (int e = 0; e < 8; ++e) v[e] = to_h<F16>(to_f32<F16>(v[e]) + to_f32<F16>(p[e]));
         }
-        *reinterpret_cast<ct_u16x8*>(out + (long long)r * C + j) = v;
+        *reinterpret_cast<u16x8*>(out + (long long)r * C + j) = v;
     }
 }
 
@@ -61,14 +39,14 @@ __global__ __launch_bounds__(256) void act16_kernel(const unsigned short* x, lon
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
         const long long m = q / d8;
         const int j = 8 * (int)(q - m * d8);
-        const ct_u16x8 v = *reinterpret_cast<const ct_u16x8*>(x + m * ldx + j);
-        ct_u16x8 o;
+        const u16x8 v = *reinterpret_cast<const u16x8*>(x + m * ldx + j);
+        u16x8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const float f = ct_to_f32<F16>(v[e]);
-            o[e] = ct_from_f32<F16>(KIND == 0 ? quick_gelu(f) : gelu_erf(f));
+            const float f = to_f32<F16>(v[e]);
+            o[e] = to_h<F16>(KIND == 0 ? quick_gelu(f) : gelu_erf(f));
         }
-        *reinterpret_cast<ct_u16x8*>(y + m * ldy + j) = o;
+        *reinterpret_cast<u16x8*>(y + m * ldy + j) = o;
     }
 }
 
@@ -80,8 +58,7 @@ static bool ct_a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u
 
 extern "C" int eegclip_gather_rows16(const void* table, long long table_rows, const void* idx, int idx64, const void* add, int add_rows, void* out, int rows, int C,
                                      int dtype, void* stream) {
-    if (!table || !idx || !out || table_rows < 1 || rows < 1 || C < 8 || C % 8 || (add && add_rows < 1) || (idx64 != 0 && idx64 != 1) ||
-        (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16))
+    if (!table || !idx || !out || table_rows < 1 || rows < 1 || C < 8 || C % 8 || (add && add_rows < 1) || (idx64 != 0 && idx64 != 1) || !half_dtype_ok(dtype))
         return EEGCLIP_EINVAL;
     if (!ct_a16(table) || !ct_a16(out) || (add && !ct_a16(add)) || (reinterpret_cast<uintptr_t>(idx) & (idx64 ? 7u : 3u))) return EEGCLIP_EALIGN;
     long long g = ((long long)rows * (C / 8) + 255) / 256;
@@ -101,7 +78,7 @@ extern "C" int eegclip_gather_rows16(const void* table, long long table_rows, co
 }
 
 extern "C" int eegclip_act16(const void* x, long long ldx, void* y, long long ldy, int M, int D, int kind, int dtype, void* stream) {
-    if (!x || !y || M < 1 || D < 8 || D % 8 || ldx < D || ldy < D || (kind != 0 && kind != 1) || (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16))
+    if (!x || !y || M < 1 || D < 8 || D % 8 || ldx < D || ldy < D || (kind != 0 && kind != 1) || !half_dtype_ok(dtype))
         return EEGCLIP_EINVAL;
     if (!ct_a16(x) || !ct_a16(y) || ldx % 8 || ldy % 8) return EEGCLIP_EALIGN;
     long long g = ((long long)M * (D / 8) + 255) / 256;

@@ -19,21 +19,9 @@
 //     NCHW (N, Cout, 2H, 2W): the layout of the pipeline's low_level_latent.
 //   epilogue           y = acc * scale[co] + shift[co] (fp32; eval-mode BatchNorm folded with the bias; scale NULL: 1, shift NULL: 0), optional ReLU, one
 //     rounding to 16 bit.  Interior pixels only: the output frame's border is never written.
-#include "attn16.h"
+#include "half16.h"
 
 namespace eeg {
-
-typedef unsigned short ct_u16x8 __attribute__((ext_vector_type(8)));
-
-template <bool F16>
-__device__ __forceinline__ float ct_to_f32(unsigned short u) {
-    if (F16) {
-        _Float16 h;
-        memcpy(&h, &u, 2);
-        return (float)h;
-    }
-    return bf16_bits_to_f32(u);
-}
 
 struct ct_args {
     const unsigned short *in, *W;
@@ -123,7 +111,7 @@ template <bool F16>
 __global__ __launch_bounds__(256) void convt_small16_kernel(const ct_args a) {
     EEG_LDS_BASE(unsigned short, wl);                                       // [phase][Cout][tap][Cin]
     const int wn8 = 2 * a.Cout * a.Cin;                                     // 16 Cout Cin elements in vectors of 8
-    for (int i = threadIdx.x; i < wn8; i += 256) reinterpret_cast<ct_u16x8*>(wl)[i] = reinterpret_cast<const ct_u16x8*>(a.W)[i];
+    for (int i = threadIdx.x; i < wn8; i += 256) reinterpret_cast<u16x8*>(wl)[i] = reinterpret_cast<const u16x8*>(a.W)[i];
     __syncthreads();
     const int Ho = 2 * a.Hi, Wo = 2 * a.Wi, Hp = a.Hi + 2, Wp = a.Wi + 2;
     const long long total = (long long)a.N * a.Cout * Ho * Wo;
@@ -140,9 +128,9 @@ __global__ __launch_bounds__(256) void convt_small16_kernel(const ct_args a) {
             const unsigned short* p = a.in + (((long long)n_ * Hp + y + 1 + ct_delta(py, tap >> 1)) * Wp + x + 1 + ct_delta(px, tap & 1)) * a.Cin;
             const unsigned short* w = wl + ((phase * a.Cout + co) * 4 + tap) * a.Cin;
             for (int ci = 0; ci < a.Cin; ci += 8) {
-                const ct_u16x8 pv = *reinterpret_cast<const ct_u16x8*>(p + ci), wv = *reinterpret_cast<const ct_u16x8*>(w + ci);
+                const u16x8 pv = *reinterpret_cast<const u16x8*>(p + ci), wv = *reinterpret_cast<const u16x8*>(w + ci);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) acc += ct_to_f32<F16>(pv[e]) * ct_to_f32<F16>(wv[e]);
+                for (int e = 0; e < 8; ++e) acc += to_f32<F16>(pv[e]) * to_f32<F16>(wv[e]);
             }
         }
         if (a.scale) acc *= a.scale[co];
@@ -160,7 +148,7 @@ constexpr int CT_SMALL_LDS = 64 * 1024;     // the direct form's packed weights:
 
 static int ct_check(const eegclip_convt16_desc* d) {
     if (!d || !d->in || !d->W || !d->out || d->N < 1 || d->Hi < 1 || d->Wi < 1 || d->Cin < 64 || d->Cin % 64 || d->Cout < 1 || d->KS != 4 || d->stride != 2 ||
-        d->pad != 1 || (d->relu != 0 && d->relu != 1) || (d->dtype != EEGCLIP_DT_BF16 && d->dtype != EEGCLIP_DT_F16))
+        d->pad != 1 || (d->relu != 0 && d->relu != 1) || !half_dtype_ok(d->dtype))
         return EEGCLIP_EINVAL;
     if (d->Hi > 16384 || d->Wi > 16384 || d->Ho != 2 * d->Hi || d->Wo != 2 * d->Wi) return EEGCLIP_EINVAL;
     if (d->Cout >= 16 ? d->Cout % 16 != 0 : (long long)32 * d->Cout * d->Cin > CT_SMALL_LDS) return EEGCLIP_EINVAL;

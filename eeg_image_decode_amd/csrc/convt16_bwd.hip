@@ -22,37 +22,11 @@
 //     summed over the pixels: an all-ones A fragment in wave 0 of the ci-tile-0 workgroups.  slabs == 1: dW is written directly (divided by loss_scale); else
 //     slab s goes to the workspace and convt_bwd_weight_reduce_kernel adds the slabs in order.  Dead taps (Hi == 1 / Wi == 1) get exact zeros, nothing read.
 //   convt_small16_bwd_weight_kernel  Cout < 16: thread = one (ci, co) with its 16 taps in registers, fp32 dz NCHW, K slabs over workgroups -> workspace -> reduce.
-#include "attn16.h"
+#include "half16.h"
 
 #include <string.h>
 
 namespace eeg {
-
-typedef short cb_s4 __attribute__((ext_vector_type(4)));
-
-template <bool F16>
-__device__ __forceinline__ float cb_to_f32(unsigned short u) {
-    if (F16) {
-        _Float16 h;
-        memcpy(&h, &u, 2);
-        return (float)h;
-    }
-    return bf16_bits_to_f32(u);
-}
-
-__device__ __forceinline__ cb_s4 cb_tr_read(const unsigned char* p) {
-#if defined(EEG_EMU)
-    const int lane = hipemu::cur->lane, g = lane >> 4, i = lane & 15;
-    cb_s4 r;
-    for (int j = 0; j < 4; ++j) {
-        const unsigned long long src = hipemu::shfl_idx((unsigned long long)(uintptr_t)p, 16 * g + 4 * j + (i >> 2));
-        r[j] = reinterpret_cast<const short*>((uintptr_t)src)[i & 3];
-    }
-    return r;
-#else
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) cb_s4*)(p));
-#endif
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------------------- pack
 constexpr int CP_T = 32;                        // tile side (ci and co)
@@ -195,7 +169,7 @@ __global__ __launch_bounds__(256) void convt_small16_bwd_data_kernel(const cbd_a
                 if (ox < 0 || ox >= Wo) continue;
                 const float* zq = a.dzf + ((long long)n_ * a.Cout * Ho + oy) * Wo + ox;
                 const unsigned short* w = wl + (4 * ky + kx) * a.Cout * a.Cin + ci;
-                for (int co = 0; co < a.Cout; ++co) acc += zq[(long long)co * Ho * Wo] * cb_to_f32<F16>(w[co * a.Cin]);
+                for (int co = 0; co < a.Cout; ++co) acc += zq[(long long)co * Ho * Wo] * to_f32<F16>(w[co * a.Cin]);
             }
         }
         a.dx[(((long long)n_ * Hp + y + 1) * Wp + x + 1) * a.Cin + ci] = to_h<F16>(acc);
@@ -234,7 +208,7 @@ __global__ __launch_bounds__(256) void convt16_bwd_weight_kernel(const cbw_args 
     const int srow = t >> 3, sch = t & 7;                                   // x staging: pixel row of the k-tile, 16-byte chunk of its 64 channels
     const int frow = 4 * g + (fr >> 2), fcol = 8 * (fr & 3);                // transpose-read role: row and byte offset within a 16-channel block
     auto frag = [&](const unsigned char* p, int rowb) {
-        const cb_s4 u = cb_tr_read(p), v = cb_tr_read(p + 16 * rowb);
+        const s16x4 u = lds_read_tr16(p), v = lds_read_tr16(p + 16 * rowb);
         return bf16x8{u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
     };
     for (int kt = kt0; kt < kt1; ++kt) {
@@ -298,7 +272,7 @@ __global__ __launch_bounds__(256) void convt_small16_bwd_weight_kernel(const cbw
     for (int k = 0; k < 16; ++k) acc[k] = 0.f;
     for (int p = p0; p < p1; ++p) {                                         // (the pixel is uniform over the workgroup: so is every bounds check)
         const int x = p % a.Wi, q1 = p / a.Wi, y = q1 % a.Hi, n_ = q1 / a.Hi;
-        const float xv = cb_to_f32<F16>(a.x[(((long long)n_ * Hp + y + 1) * Wp + x + 1) * a.Cin + ci]);
+        const float xv = to_f32<F16>(a.x[(((long long)n_ * Hp + y + 1) * Wp + x + 1) * a.Cin + ci]);
         const float* zq = a.dzf + ((long long)n_ * a.Cout + co) * Ho * Wo;
 #pragma unroll
         for (int ky = 0; ky < 4; ++ky) {

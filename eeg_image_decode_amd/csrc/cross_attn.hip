@@ -9,7 +9,7 @@
 // xor-shuffles (16, 32), and the probabilities are already in A-operand order for P V -- no LDS round trip for P.
 // The k-slot permutation this implies (tile pair 2u/2u+1, rows 4g+r) is matched on the V side by reading V^T with two
 // 8-byte LDS reads per lane.  Both branches accumulate into the same fp32 accumulators (ip probabilities pre-scaled).
-#include "attn16.h"
+#include "half16.h"
 
 #include <stdlib.h>
 
@@ -20,8 +20,6 @@ constexpr int CA_MAXT = 8;        // key tiles of 16 -> S <= 128
 constexpr int CA_KLD = CA_D + 16; // K row stride in halfs (160 B = 16 B * 10: the 16 lanes of a ds_read_b128 service group hit 16 distinct slots;
                                   // 144 B measured 5.8 conflict cycles per LDS instruction)
 constexpr int CA_QB = 512;        // queries per workgroup (4 waves x 8 tiles of 16): the K / V^T staging of a (sample, head) is amortised over them
-
-typedef unsigned int ca_u32x4 __attribute__((ext_vector_type(4)));
 
 // V^T row stride in halfs for nt key tiles: >= 32 * ceil(nt / 2) keys and = 4 (mod 64), i.e. 2 dwords (mod 32): the 16 lanes of a
 // service group of the paired 8-byte reads (ds_read2_b64, 32 banks) then walk all 32 banks (a 208-byte stride measured 4.7 conflict
@@ -134,15 +132,15 @@ __device__ __forceinline__ void branch(const unsigned short* Ks, const unsigned 
         if (2 * u >= ntile) break;
         const bool two = 2 * u + 1 < ntile;
         const f32x4 lo4 = s[2 * u], hi4 = two ? s[2 * u + 1] : f32x4{0.f, 0.f, 0.f, 0.f};
-        const ca_u32x4 pw{pack2<F16>(lo4[0] * nrm, lo4[1] * nrm), pack2<F16>(lo4[2] * nrm, lo4[3] * nrm),
-                          pack2<F16>(hi4[0] * nrm, hi4[1] * nrm), pack2<F16>(hi4[2] * nrm, hi4[3] * nrm)};
+        const u32x4 pw{pack2<F16>(lo4[0] * nrm, lo4[1] * nrm), pack2<F16>(lo4[2] * nrm, lo4[3] * nrm),
+                       pack2<F16>(hi4[0] * nrm, hi4[1] * nrm), pack2<F16>(hi4[2] * nrm, hi4[3] * nrm)};
         const bf16x8 pa = __builtin_bit_cast(bf16x8, pw);
 #pragma unroll
         for (int dn = 0; dn < 4; ++dn) {
             const unsigned short* vp = Vt + (16 * dn + fr) * ldv + 32 * u + 4 * g;
             const uint2 lo = *reinterpret_cast<const uint2*>(vp);
             const uint2 hi = *reinterpret_cast<const uint2*>(vp + 16);
-            const bf16x8 bv = __builtin_bit_cast(bf16x8, (ca_u32x4{lo.x, lo.y, hi.x, hi.y}));
+            const bf16x8 bv = __builtin_bit_cast(bf16x8, (u32x4{lo.x, lo.y, hi.x, hi.y}));
             acc[dn] = mma<F16>(bv, pa, acc[dn]);                       // O^T[d = 16dn + 4g + r][query = fr]: 4 consecutive d per lane
         }
     }
@@ -224,7 +222,7 @@ __device__ __forceinline__ void load_frag(kv_frag<NT>& f, const unsigned short* 
             const unsigned short* vp = Vt + (16 * dn + fr) * ldv + 32 * u + 4 * g;
             const uint2 lo = *reinterpret_cast<const uint2*>(vp);
             const uint2 hi = *reinterpret_cast<const uint2*>(vp + 16);
-            f.v[u][dn] = __builtin_bit_cast(bf16x8, (ca_u32x4{lo.x, lo.y, hi.x, hi.y}));
+            f.v[u][dn] = __builtin_bit_cast(bf16x8, (u32x4{lo.x, lo.y, hi.x, hi.y}));
         }
 }
 
@@ -280,8 +278,8 @@ __device__ __forceinline__ void branch_reg2(const kv_frag<NT>& f, const unsigned
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             const f32x4 lo4 = s[p][2 * u], hi4 = two ? s[p][two ? 2 * u + 1 : 0] : f32x4{0.f, 0.f, 0.f, 0.f};
-            const ca_u32x4 pw{pack2<F16>(lo4[0] * nrm[p], lo4[1] * nrm[p]), pack2<F16>(lo4[2] * nrm[p], lo4[3] * nrm[p]),
-                              pack2<F16>(hi4[0] * nrm[p], hi4[1] * nrm[p]), pack2<F16>(hi4[2] * nrm[p], hi4[3] * nrm[p])};
+            const u32x4 pw{pack2<F16>(lo4[0] * nrm[p], lo4[1] * nrm[p]), pack2<F16>(lo4[2] * nrm[p], lo4[3] * nrm[p]),
+                           pack2<F16>(hi4[0] * nrm[p], hi4[1] * nrm[p]), pack2<F16>(hi4[2] * nrm[p], hi4[3] * nrm[p])};
             pa[p] = __builtin_bit_cast(bf16x8, pw);
         }
 #pragma unroll
@@ -293,7 +291,7 @@ __device__ __forceinline__ void branch_reg2(const kv_frag<NT>& f, const unsigned
                 const unsigned short* vp = Vt + (16 * dn + fr) * ldv + 32 * u + 4 * g;
                 const uint2 lo = *reinterpret_cast<const uint2*>(vp);
                 const uint2 hi = *reinterpret_cast<const uint2*>(vp + 16);
-                bv = __builtin_bit_cast(bf16x8, (ca_u32x4{lo.x, lo.y, hi.x, hi.y}));
+                bv = __builtin_bit_cast(bf16x8, (u32x4{lo.x, lo.y, hi.x, hi.y}));
             }
 #pragma unroll
             for (int p = 0; p < 2; ++p) acc[p][dn] = mma<F16>(bv, pa[p], acc[p][dn]);
@@ -383,7 +381,7 @@ extern "C" int eegclip_cross_attn_fwd(const void* q, const void* k, const void* 
     if (!q || !k || !v || !out || B < 1 || HW < 1 || heads < 1 || head_dim != CA_D || S < 1 || S > 16 * CA_MAXT || S_ip < 0 || S_ip > 16 * CA_MAXT)
         return EEGCLIP_EINVAL;
     if (S_ip > 0 && (!k_ip || !v_ip)) return EEGCLIP_EINVAL;
-    if (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16) return EEGCLIP_EINVAL;
+    if (!half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
     if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)k_ip | (uintptr_t)v_ip | (uintptr_t)out) & 15) != 0) return EEGCLIP_EALIGN;
     ca_args a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (const unsigned short*)k_ip, (const unsigned short*)v_ip,
               (unsigned short*)out, B, HW, heads, S, S_ip, 0.125f * 1.44269504088896340736f, ip_scale};      // scale * log2(e): base-2 softmax

@@ -310,6 +310,35 @@ __device__ __forceinline__ f32x16 mfma_bf16_32x32x16(bf16x8 a, bf16x8 b, f32x16 
 #endif
 }
 
+// ---- transposed LDS read and scheduler fence (the 16-bit kernels get them through csrc/half16.h; the bf16x3 kernels use them on their planes) ----
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+
+// ds_read_b64_tr_b16: per 16-lane group, lane 4q+p addresses row q, columns 4p..4p+3 of a 4 x 16 block of 16-bit elements; lane i receives column i,
+// row q in element q -- i.e. element q is the (i & 3)-th element of the 8 bytes addressed by lane 4q + (i >> 2).  (EXEC must be full: called outside
+// any lane-dependent branch.)
+__device__ __forceinline__ s16x4 lds_read_tr16(const void* p) {
+#if defined(EEG_EMU)
+    auto all = hipemu::wave_allgather(&p, sizeof(p));
+    const int l = hipemu::cur->lane, grp = l & ~15, i = l & 15;
+    s16x4 r;
+    for (int q = 0; q < 4; ++q) {
+        const short* src;
+        memcpy(&src, all[grp + 4 * q + (i >> 2)], sizeof(src));
+        r[q] = src[i & 3];
+    }
+    return r;
+#else
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
+#endif
+}
+
+// the instruction scheduler moves nothing across this point
+__device__ __forceinline__ void sched_fence() {
+#if !defined(EEG_EMU)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+}
+
 // ---- two-level index -> element offset  (eegclip_dim: offset(i) = (i / div) * so + (i % div) * si) ----
 __device__ __forceinline__ long long dim_off(const eegclip_dim& d, int i) {
     if ((long long)i < d.div) return (long long)i * d.si;      // plain strided dimension (div = 2^62) or first run

@@ -13,7 +13,7 @@
 // quad of accumulator registers is 4 consecutive n -> 8-byte stores, bias / residual fetched as 8 bytes.
 // Requirements: N % 128 == 0, K % 64 == 0, leading dimensions multiples of 8, 16-byte aligned pointers; any M (rows are clamped on the
 // load side and predicated on the store side).  XCD-aware tile order (n fastest inside an XCD's run: the A panel is shared).
-#include "eeg_common.h"
+#include "half16.h"
 
 #include <stdlib.h>
 
@@ -29,57 +29,6 @@ constexpr int G16_ROWB = 2 * G16_K;                       // 128-byte LDS rows
 constexpr int G16_TILE_B = G16_T * G16_ROWB;              // one operand tile
 constexpr int G16_STAGE_B = 2 * G16_TILE_B;
 
-typedef _Float16 g16_f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x16 mfma_f16_32x32x16(bf16x8 a, bf16x8 b, f32x16 c) {
-#if defined(EEG_EMU)
-    struct AB { bf16x8 a, b; } in{a, b};
-    auto all = hipemu::wave_allgather(&in, sizeof(in));
-    const int l = hipemu::cur->lane, col = l & 31, hb = 4 * (l >> 5);
-    f32x16 d = c;
-    for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + hb;
-        float acc = c[r];
-        for (int h = 0; h < 2; ++h) {
-            AB ra, rbv;
-            memcpy(&ra, all[row + 32 * h], sizeof(AB));
-            memcpy(&rbv, all[col + 32 * h], sizeof(AB));
-            for (int e = 0; e < 8; ++e) {
-                _Float16 x, y;
-                short sx = ra.a[e], sy = rbv.b[e];
-                memcpy(&x, &sx, 2);
-                memcpy(&y, &sy, 2);
-                acc += (float)x * (float)y;
-            }
-        }
-        d[r] = acc;
-    }
-    return d;
-#else
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(g16_f16x8, a), __builtin_bit_cast(g16_f16x8, b), c, 0, 0, 0);
-#endif
-}
-
-template <bool F16>
-__device__ __forceinline__ float g16_to_f32(unsigned short u) {
-    if (F16) {
-        _Float16 h;
-        memcpy(&h, &u, 2);
-        return (float)h;
-    }
-    return bf16_bits_to_f32(u);
-}
-template <bool F16>
-__device__ __forceinline__ unsigned short g16_from_f32(float v) {
-    if (F16) {
-        const _Float16 h = (_Float16)v;
-        unsigned short u;
-        memcpy(&u, &h, 2);
-        return u;
-    }
-    return f32_to_bf16_bits(v);
-}
-
 struct g16_args {
     const unsigned short* A;
     const unsigned short* W;
@@ -90,8 +39,6 @@ struct g16_args {
     int M, N, K, r_div;
     int tiles_n, ntiles, chunk;
 };
-
-typedef unsigned short g16_u16x4 __attribute__((ext_vector_type(4)));
 
 template <bool F16>
 __global__ __launch_bounds__(256) void gemm16_kernel(const g16_args a) {
@@ -163,21 +110,17 @@ __global__ __launch_bounds__(256) void gemm16_kernel(const g16_args a) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             if (s + 1 < 4) read_step(s + 1, (s + 1) & 1);
-#if !defined(EEG_EMU)
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            sched_fence();
             const int set = s & 1;
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    acc[j][i] = F16 ? mfma_f16_32x32x16(wf[set][j], am[set][i], acc[j][i]) : mfma_bf16_32x32x16(wf[set][j], am[set][i], acc[j][i]);
+                    acc[j][i] = mma32<F16>(wf[set][j], am[set][i], acc[j][i]);
                     const int mi = 4 * s + 2 * j + i;          // one DMA instruction after every second MFMA
                     if (refill && (mi & 1)) issue_one(kt + G16_NS - 1, mi >> 1);
                 }
-#if !defined(EEG_EMU)
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            sched_fence();
         }
     }
     // ---- epilogue: lane (r32, h) owns row m = m0 + 64 wm + 32 i + r32; registers 4 eq .. 4 eq + 3 of n tile j are the 4 consecutive columns
@@ -195,18 +138,18 @@ __global__ __launch_bounds__(256) void gemm16_kernel(const g16_args a) {
 #pragma unroll
             for (int eq = 0; eq < 4; ++eq) {
                 const int n = n0 + wn * 64 + 32 * j + 8 * eq + 4 * h;
-                g16_u16x4 bv = g16_u16x4{0, 0, 0, 0}, rv = g16_u16x4{0, 0, 0, 0};
-                if (bias) bv = *reinterpret_cast<const g16_u16x4*>(bias + n);
-                if (rrow) rv = *reinterpret_cast<const g16_u16x4*>(rrow + n);
-                g16_u16x4 o;
+                u16x4 bv = u16x4{0, 0, 0, 0}, rv = u16x4{0, 0, 0, 0};
+                if (bias) bv = *reinterpret_cast<const u16x4*>(bias + n);
+                if (rrow) rv = *reinterpret_cast<const u16x4*>(rrow + n);
+                u16x4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float v = acc[j][i][4 * eq + e];
-                    if (bias) v += g16_to_f32<F16>(bv[e]);
-                    if (rrow) v += g16_to_f32<F16>(rv[e]);
-                    o[e] = g16_from_f32<F16>(v);
+                    if (bias) v += to_f32<F16>(bv[e]);
+                    if (rrow) v += to_f32<F16>(rv[e]);
+                    o[e] = to_h<F16>(v);
                 }
-                *reinterpret_cast<g16_u16x4*>(crow + n) = o;
+                *reinterpret_cast<u16x4*>(crow + n) = o;
             }
     }
 }
@@ -223,24 +166,24 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const unsigned short*
                                                             unsigned short* __restrict__ out, unsigned short* __restrict__ scaled, float g, float cx, float ce,
                                                             float cn, float in_scale, long long n4) {
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += (long long)gridDim.x * blockDim.x) {
-        const g16_u16x4 xv = *reinterpret_cast<const g16_u16x4*>(x + 4 * q);
-        const g16_u16x4 eu = *reinterpret_cast<const g16_u16x4*>(eps_u + 4 * q);
-        g16_u16x4 ec = eu, nz = g16_u16x4{0, 0, 0, 0};
-        if (eps_c) ec = *reinterpret_cast<const g16_u16x4*>(eps_c + 4 * q);
-        if (noise) nz = *reinterpret_cast<const g16_u16x4*>(noise + 4 * q);
-        g16_u16x4 o, so;
+        const u16x4 xv = *reinterpret_cast<const u16x4*>(x + 4 * q);
+        const u16x4 eu = *reinterpret_cast<const u16x4*>(eps_u + 4 * q);
+        u16x4 ec = eu, nz = u16x4{0, 0, 0, 0};
+        if (eps_c) ec = *reinterpret_cast<const u16x4*>(eps_c + 4 * q);
+        if (noise) nz = *reinterpret_cast<const u16x4*>(noise + 4 * q);
+        u16x4 o, so;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float u = g16_to_f32<F16>(eu[e]);
+            const float u = to_f32<F16>(eu[e]);
             float eps = u;
-            if (eps_c) eps = u + g * (g16_to_f32<F16>(ec[e]) - u);
-            float v = cx * g16_to_f32<F16>(xv[e]) + ce * eps;
-            if (noise) v += cn * g16_to_f32<F16>(nz[e]);
-            o[e] = g16_from_f32<F16>(v);
-            so[e] = g16_from_f32<F16>(g16_to_f32<F16>(o[e]) * in_scale);      // the model sees the ROUNDED latent, like the reference's 16-bit tensors
+            if (eps_c) eps = u + g * (to_f32<F16>(ec[e]) - u);
+            float v = cx * to_f32<F16>(xv[e]) + ce * eps;
+            if (noise) v += cn * to_f32<F16>(nz[e]);
+            o[e] = to_h<F16>(v);
+            so[e] = to_h<F16>(to_f32<F16>(o[e]) * in_scale);      // the model sees the ROUNDED latent, like the reference's 16-bit tensors
         }
-        *reinterpret_cast<g16_u16x4*>(out + 4 * q) = o;
-        if (scaled) *reinterpret_cast<g16_u16x4*>(scaled + 4 * q) = so;
+        *reinterpret_cast<u16x4*>(out + 4 * q) = o;
+        if (scaled) *reinterpret_cast<u16x4*>(scaled + 4 * q) = so;
     }
 }
 
@@ -250,7 +193,7 @@ using namespace eeg;
 
 extern "C" int eegclip_gemm16(const void* A, long long lda, const void* W, long long ldw, void* C, long long ldc, const void* bias, const void* R,
                               long long ldr, int r_div, int M, int N, int K, int dtype, void* stream) {
-    if (!A || !W || !C || M < 0 || N < 1 || K < 1 || (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16)) return EEGCLIP_EINVAL;
+    if (!A || !W || !C || M < 0 || N < 1 || K < 1 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
     if (N % G16_T || K % G16_K || (lda & 7) || (ldw & 7) || (ldc & 3) || lda < K || ldw < K || ldc < N || r_div < 0 || (R && (ldr < N || (ldr & 3)))) return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15u) return EEGCLIP_EALIGN;
     if ((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(R)) & 7u) return EEGCLIP_EALIGN;
@@ -274,7 +217,7 @@ extern "C" int eegclip_gemm16(const void* A, long long lda, const void* W, long 
 
 extern "C" int eegclip_sampler_step(const void* x, const void* eps_u, const void* eps_c, const void* noise, void* out, void* scaled, float guidance,
                                     float cx, float ce, float cn, float in_scale, long long n, int dtype, void* stream) {
-    if (!x || !eps_u || !out || n < 0 || (n & 3) || (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16)) return EEGCLIP_EINVAL;
+    if (!x || !eps_u || !out || n < 0 || (n & 3) || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(eps_u) | reinterpret_cast<uintptr_t>(eps_c) | reinterpret_cast<uintptr_t>(noise) |
          reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(scaled)) & 7u)
         return EEGCLIP_EALIGN;

@@ -1,5 +1,7 @@
-// 16-bit attention helpers shared by csrc/cross_attn.hip and csrc/self_attn.hip: the f16 form of the 16x16x32 MFMA (the bf16 form is in
-// eeg_common.h), fp32 -> 16-bit rounding, and the base-2 exponent of the softmax.
+// The 16-bit (fp16 / bf16 I/O) device layer, one definition each, shared by every 16-bit kernel file (gemm16, vae, unet, clip_text, caption, convt16,
+// convt16_bwd, bn2d16, cross_attn, self_attn, vae_attn): the vector types, 16-bit <-> fp32 conversion selected by the template flag F16, the f16 forms
+// of the 16x16x32 and 32x32x16 MFMAs (the bf16 forms are in eeg_common.h) with their selectors, the base-2 exponent of the softmax, and the host-side
+// dtype check.  The transposed LDS read (lds_read_tr16, s16x4) and sched_fence() come with eeg_common.h.
 #pragma once
 
 #include "eeg_common.h"
@@ -7,6 +9,11 @@
 namespace eeg {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+inline bool half_dtype_ok(int dtype) { return dtype == EEGCLIP_DT_BF16 || dtype == EEGCLIP_DT_F16; }
 
 __device__ __forceinline__ f32x4 mfma_f16_16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {
 #if defined(EEG_EMU)
@@ -36,6 +43,45 @@ __device__ __forceinline__ f32x4 mfma_f16_16x16x32(bf16x8 a, bf16x8 b, f32x4 c) 
 #endif
 }
 
+// 32x32x16 f16: the fragment layout of mfma_bf16_32x32x16 (eeg_common.h)
+__device__ __forceinline__ f32x16 mfma_f16_32x32x16(bf16x8 a, bf16x8 b, f32x16 c) {
+#if defined(EEG_EMU)
+    struct AB { bf16x8 a, b; } in{a, b};
+    auto all = hipemu::wave_allgather(&in, sizeof(in));
+    const int l = hipemu::cur->lane, col = l & 31, hb = 4 * (l >> 5);
+    f32x16 d = c;
+    for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + hb;
+        float acc = c[r];
+        for (int h = 0; h < 2; ++h) {
+            AB ra, rbv;
+            memcpy(&ra, all[row + 32 * h], sizeof(AB));
+            memcpy(&rbv, all[col + 32 * h], sizeof(AB));
+            for (int e = 0; e < 8; ++e) {
+                _Float16 x, y;
+                short sx = ra.a[e], sy = rbv.b[e];
+                memcpy(&x, &sx, 2);
+                memcpy(&y, &sy, 2);
+                acc += (float)x * (float)y;
+            }
+        }
+        d[r] = acc;
+    }
+    return d;
+#else
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+#endif
+}
+
+template <bool F16>
+__device__ __forceinline__ float to_f32(unsigned short u) {
+    if (F16) {
+        _Float16 h;
+        memcpy(&h, &u, 2);
+        return (float)h;
+    }
+    return bf16_bits_to_f32(u);
+}
 template <bool F16>
 __device__ __forceinline__ unsigned short to_h(float v) {
     if (F16) {
@@ -70,6 +116,10 @@ __device__ __forceinline__ float fast_exp2(float x) {
 template <bool F16>
 __device__ __forceinline__ f32x4 mma(bf16x8 a, bf16x8 b, f32x4 c) {
     return F16 ? mfma_f16_16x16x32(a, b, c) : mfma_bf16_16x16x32(a, b, c);
+}
+template <bool F16>
+__device__ __forceinline__ f32x16 mma32(bf16x8 a, bf16x8 b, f32x16 c) {
+    return F16 ? mfma_f16_32x32x16(a, b, c) : mfma_bf16_32x32x16(a, b, c);
 }
 
 }  // namespace eeg

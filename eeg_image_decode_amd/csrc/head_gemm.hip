@@ -57,22 +57,6 @@ __device__ __forceinline__ int hg_swz_t(int row) { return ((row >> 1) & 1) << 2;
 
 __device__ __forceinline__ int hg_swz(int row) { return (row >> 2) & 3; }
 
-typedef short hg_s4 __attribute__((ext_vector_type(4)));
-// LDS transpose read: within a 16-lane group, lane i receives as element j the (i & 3)-th 16-bit element of the 8 bytes addressed by lane 4 j + (i >> 2)
-__device__ __forceinline__ hg_s4 hg_tr_read(const unsigned char* p) {
-#if defined(EEG_EMU)
-    const int lane = hipemu::cur->lane, g = lane >> 4, i = lane & 15;
-    hg_s4 r;
-    for (int j = 0; j < 4; ++j) {
-        const unsigned long long src = hipemu::shfl_idx((unsigned long long)(uintptr_t)p, 16 * g + 4 * j + (i >> 2));
-        r[j] = reinterpret_cast<const short*>((uintptr_t)src)[i & 3];
-    }
-    return r;
-#else
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) hg_s4*)(p));
-#endif
-}
-
 template <bool BT>
 __global__ __launch_bounds__(512, 2) void head_gemm_kernel(const hg_args a) {
     EEG_LDS_BASE(unsigned char, lds);
@@ -162,8 +146,8 @@ __global__ __launch_bounds__(512, 2) void head_gemm_kernel(const hg_args a) {
                 ah[s] = *reinterpret_cast<const bf16x8*>(st + foa[s]);
                 al[s] = *reinterpret_cast<const bf16x8*>(st + 2 * HG_TILE_B + foa[s]);
                 if (BT) {
-                    const hg_s4 x = hg_tr_read(st + fob[s]), y = hg_tr_read(st + fob[s] + 4 * 128);
-                    const hg_s4 xl = hg_tr_read(st + 2 * HG_TILE_B + fob[s]), yl = hg_tr_read(st + 2 * HG_TILE_B + fob[s] + 4 * 128);
+                    const s16x4 x = lds_read_tr16(st + fob[s]), y = lds_read_tr16(st + fob[s] + 4 * 128);
+                    const s16x4 xl = lds_read_tr16(st + 2 * HG_TILE_B + fob[s]), yl = lds_read_tr16(st + 2 * HG_TILE_B + fob[s] + 4 * 128);
                     bh[s] = bf16x8{x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
                     bl[s] = bf16x8{xl[0], xl[1], xl[2], xl[3], yl[0], yl[1], yl[2], yl[3]};
                 } else {

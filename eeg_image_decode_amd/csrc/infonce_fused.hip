@@ -209,9 +209,7 @@ __global__ __launch_bounds__(64 * (NW + NPRD)) void infonce_tile_kernel(const if
         read_step(0, 0);
 #pragma unroll
         for (int s = 0; s < NSTEP; ++s) {
-#if !defined(EEG_EMU)
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            sched_fence();
             const int set = s & 1;
 #pragma unroll
             for (int j = 0; j < WTK; ++j)
@@ -228,18 +226,12 @@ __global__ __launch_bounds__(64 * (NW + NPRD)) void infonce_tile_kernel(const if
                     acc[j][i] = mfma_bf16_32x32x16(kh[set][j], qh[set][i], acc[j][i]);      // D[key 32j + row(reg, h)][query 32i + r32]
                     if (!SPEC && refill && ((m0_ + last + 1) * DPT) / TOTAL > ((m0_ + last) * DPT) / TOTAL) issue_one(kt + IF_NS - 1, ((m0_ + last) * DPT) / TOTAL);
                     if (j == 0 && i == 0 && s + 1 < NSTEP) {
-#if !defined(EEG_EMU)
-                        __builtin_amdgcn_sched_barrier(0);
-#endif
+                        sched_fence();
                         read_step(s + 1, (s + 1) & 1);
-#if !defined(EEG_EMU)
-                        __builtin_amdgcn_sched_barrier(0);
-#endif
+                        sched_fence();
                     }
                 }
-#if !defined(EEG_EMU)
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            sched_fence();
         }
     };
     if (PF) {
@@ -307,19 +299,13 @@ __global__ __launch_bounds__(64 * (NW + NPRD)) void infonce_tile_kernel(const if
                         if (j == 0 && i == 0) {
                             // the next step's fragment reads go out BEHIND this step's first MFMA: the s_waitcnt lgkmcnt(0) the compiler puts in front of that MFMA
                             // (it does not count LDS reads across the loop edge) then covers only reads issued a whole step ago
-#if !defined(EEG_EMU)
-                            __builtin_amdgcn_sched_barrier(0);
-#endif
+                            sched_fence();
                             if (s + 1 < NSTEP) read_step(kt, s + 1, set ^ 1);
                             else read_step(more ? kt + 1 : kt, 0, set ^ 1);      // (unconditional: a branch here makes the compiler's LDS counts conservative; the last tile re-reads itself)
-#if !defined(EEG_EMU)
-                            __builtin_amdgcn_sched_barrier(0);
-#endif
+                            sched_fence();
                         }
                     }
-#if !defined(EEG_EMU)
-                __builtin_amdgcn_sched_barrier(0);
-#endif
+                sched_fence();
             }
         }
     } else if (!SPEC) {

@@ -88,9 +88,7 @@ __global__ __launch_bounds__(256) void logits_bf16_dma_kernel(const unsigned sho
 #pragma unroll
             for (int j = 0; j < 4; ++j) bv[s][j] = *reinterpret_cast<const bf16x8*>(bs + (wc * 64 + 16 * j + fr) * LB_K + pc);
         }
-#if !defined(EEG_EMU)
-        __builtin_amdgcn_sched_barrier(0);       // keep the 16 reads ahead of the MFMAs (the scheduler otherwise sinks each read to its use)
-#endif
+        sched_fence();       // keep the 16 reads ahead of the MFMAs (the scheduler otherwise sinks each read to its use)
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll

@@ -27,7 +27,7 @@
 // runtime bound, key j reaches query i iff j < max(i + 1, prefix) -- the image tokens see each other, everything after them is causal.  prefix = 0 is the
 // causal form, bit for bit (the same instructions on the same operands).  A workgroup's key loop ends at max(its last query + 1, prefix) and only the
 // tiles that reach past max(its first query + 1, prefix) are masked.
-#include "attn16.h"
+#include "flash16.h"
 
 namespace eeg {
 
@@ -35,9 +35,6 @@ constexpr int SA_D = 64;        // head_dim
 constexpr int SA_KT = 64;       // keys per LDS tile
 constexpr int SA_LD = SA_D + 16;  // LDS row stride in halfs (160 B), K and V
 constexpr int SA_TILE = SA_KT * SA_LD;  // halfs per K (or V) tile buffer
-
-typedef unsigned int sa_u32x4 __attribute__((ext_vector_type(4)));
-typedef short sa_s16x4 __attribute__((ext_vector_type(4)));
 
 struct sa_args {
     const unsigned short *q, *k, *v;
@@ -47,24 +44,6 @@ struct sa_args {
     float scale2;   // scale * log2(e)
     int prefix;     // CAUSAL only: keys < prefix are visible to every query (0: plain causal)
 };
-
-// ds_read_b64_tr_b16: per 16-lane group, lane 4q+p addresses row q, columns 4p..4p+3 of a 4 x 16 block; lane i receives column i, row q in
-// element q.  (EXEC must be full: called outside any lane-dependent branch.)
-__device__ __forceinline__ sa_s16x4 lds_read_tr16(const unsigned short* p) {
-#if defined(EEG_EMU)
-    auto all = hipemu::wave_allgather(&p, sizeof(p));
-    const int l = hipemu::cur->lane, grp = l & ~15, i = l & 15;
-    sa_s16x4 r;
-    for (int q = 0; q < 4; ++q) {
-        const unsigned short* src;
-        memcpy(&src, all[grp + 4 * q + (i >> 2)], sizeof(src));
-        r[q] = (short)src[i & 3];
-    }
-    return r;
-#else
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) sa_s16x4*)(p));
-#endif
-}
 
 // 16-byte pieces of one 64 x 64 tile per thread (256 threads): 2 of K, 2 of V
 struct sa_stage {
@@ -191,11 +170,7 @@ __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
 #pragma unroll
             for (int dn = 0; dn < 4; ++dn) acc[p][dn] *= alpha;
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const f32x4 lo4 = s[p][2 * u], hi4 = s[p][2 * u + 1];
-                const sa_u32x4 pw{pack2<F16>(lo4[0], lo4[1]), pack2<F16>(lo4[2], lo4[3]), pack2<F16>(hi4[0], hi4[1]), pack2<F16>(hi4[2], hi4[3])};
-                pa[p][u] = __builtin_bit_cast(bf16x8, pw);
-            }
+            for (int u = 0; u < 2; ++u) pa[p][u] = flash_pack_p<F16>(s[p][2 * u], s[p][2 * u + 1]);
         }
         // P V: k-step u covers key tiles 2u, 2u+1; lane (query fr, group g) supplies keys {32u+4g+r} U {32u+16+4g+r}; the V^T fragment
         // (d = 16dn + fr, the same keys) is two transposed reads of rows 32u+4g.. / 32u+16+4g.., lane 4q+p addressing row q, columns 4p..
@@ -204,7 +179,7 @@ __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
 #pragma unroll
             for (int dn = 0; dn < 4; ++dn) {
                 const unsigned short* vp = Vs + (32 * u + 4 * g + (fr >> 2)) * SA_LD + 16 * dn + 4 * (fr & 3);
-                const sa_s16x4 lo = lds_read_tr16(vp), hi = lds_read_tr16(vp + 16 * SA_LD);
+                const s16x4 lo = lds_read_tr16(vp), hi = lds_read_tr16(vp + 16 * SA_LD);
                 const bf16x8 bv = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
                 for (int p = 0; p < QT; ++p) acc[p][dn] = mma<F16>(bv, pa[p][u], acc[p][dn]);   // O^T[d = 16dn + 4g + r][query fr]
@@ -217,20 +192,12 @@ __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
     }
 #pragma unroll
     for (int p = 0; p < QT; ++p) {
-        float sum = l[p];
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        const float inv = 1.0f / sum;
+        const float inv = flash_row_inv(l[p]);
         const int qrow = blockIdx.x * (64 * QT) + (p * 4 + wave) * 16 + fr;
-        if (qrow < a.Tq) {                                                 // O^T tile: 8-byte stores of 4 consecutive d
+        if (qrow < a.Tq) {
             unsigned short* op = a.out + ((long long)b * a.Tq + qrow) * a.ldo + h * SA_D + 4 * g;
 #pragma unroll
-            for (int dn = 0; dn < 4; ++dn) {
-                uint2 w;
-                w.x = pack2<F16>(acc[p][dn][0] * inv, acc[p][dn][1] * inv);
-                w.y = pack2<F16>(acc[p][dn][2] * inv, acc[p][dn][3] * inv);
-                *reinterpret_cast<uint2*>(op + 16 * dn) = w;
-            }
+            for (int dn = 0; dn < 4; ++dn) flash_store4<F16>(op + 16 * dn, acc[p][dn], inv);
         }
     }
 }
@@ -248,14 +215,13 @@ extern "C" int eegclip_self_attn_supported(int head_dim, long long ldq, long lon
 
 static int sa_forward(bool causal, int prefix, const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B, int Tq,
                       int Tk, int heads, int head_dim, float scale, int dtype, void* stream) {
-    const int rc = eegclip_self_attn_supported(head_dim, ldq, ldk, ldv, ldo);
+    int rc = eegclip_self_attn_supported(head_dim, ldq, ldk, ldv, ldo);
     if (rc) return rc;
-    if (!q || !k || !v || !out || B < 1 || Tq < 1 || Tk < 1 || heads < 1 || B > 65535 || heads > 65535 || !(scale > 0.f) || !(scale < INFINITY)) return EEGCLIP_EINVAL;
-    if (causal && (Tq != Tk || prefix < 0 || prefix > Tk)) return EEGCLIP_EINVAL;
-    if (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16) return EEGCLIP_EINVAL;
+    if (heads < 1 || heads > 65535 || (causal && (Tq != Tk || prefix < 0 || prefix > Tk))) return EEGCLIP_EINVAL;
     const long long C = (long long)heads * SA_D;
     if (ldq < C || ldk < C || ldv < C || ldo < C) return EEGCLIP_EINVAL;
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) != 0) return EEGCLIP_EALIGN;
+    rc = flash_args_ok(q, k, v, out, B, Tq, Tk, scale, dtype);            // (0 = fine)
+    if (rc) return rc;
     const sa_args a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (unsigned short*)out, ldq, ldk, ldv, ldo, Tq, Tk,
                     scale * 1.44269504088896340736f, prefix};
     const size_t lds = sizeof(unsigned short) * 4 * SA_TILE;                // 40 KB: two (K, V) tile buffers

@@ -5,31 +5,9 @@
 //   geglu16      the feed-forward's GEGLU: a * gelu_erf(g) for the [value | gate] halves of ff.net.0.proj's output row
 //   concat16     the up blocks' skip concatenation cat([h, skip], channel) of two padded NHWC frames, interior pixels only (the frame pool relies on borders
 //                that no launch writes: vae.py)
-#include "eeg_common.h"
+#include "half16.h"
 
 namespace eeg {
-
-typedef unsigned short un_u16x8 __attribute__((ext_vector_type(8)));
-
-template <bool F16>
-__device__ __forceinline__ float un_to_f32(unsigned short u) {
-    if (F16) {
-        _Float16 h;
-        memcpy(&h, &u, 2);
-        return (float)h;
-    }
-    return bf16_bits_to_f32(u);
-}
-template <bool F16>
-__device__ __forceinline__ unsigned short un_from_f32(float v) {
-    if (F16) {
-        const _Float16 h = (_Float16)v;
-        unsigned short u;
-        memcpy(&u, &h, 2);
-        return u;
-    }
-    return f32_to_bf16_bits(v);
-}
 
 constexpr int LN16_MAXV = 8;                                  // 8-channel vectors per lane: C <= 64 * 8 * 8 = 4096
 
@@ -41,15 +19,15 @@ __global__ __launch_bounds__(256) void layernorm16_kernel(const unsigned short* 
     if (r >= rows) return;                                    // (wave-uniform: no barrier below)
     const unsigned short* xr = x + (long long)r * ldx;
     const int nv = C / 8;
-    un_u16x8 v[LN16_MAXV];
+    u16x8 v[LN16_MAXV];
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < LN16_MAXV; ++i) {
         const int c8 = lane + 64 * i;
         if (c8 < nv) {
-            v[i] = *reinterpret_cast<const un_u16x8*>(xr + 8 * c8);
+            v[i] = *reinterpret_cast<const u16x8*>(xr + 8 * c8);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) s += un_to_f32<F16>(v[i][e]);
+            for (int e = 0; e < 8; ++e) s += to_f32<F16>(v[i][e]);
         }
     }
     const float mean = wave_sum(s) / (float)C;
@@ -59,7 +37,7 @@ __global__ __launch_bounds__(256) void layernorm16_kernel(const unsigned short* 
         if (lane + 64 * i < nv) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float d = un_to_f32<F16>(v[i][e]) - mean;
+                const float d = to_f32<F16>(v[i][e]) - mean;
                 q += d * d;
             }
         }
@@ -69,11 +47,11 @@ __global__ __launch_bounds__(256) void layernorm16_kernel(const unsigned short* 
     for (int i = 0; i < LN16_MAXV; ++i) {
         const int c8 = lane + 64 * i;
         if (c8 < nv) {
-            const un_u16x8 g = *reinterpret_cast<const un_u16x8*>(gamma + 8 * c8), b = *reinterpret_cast<const un_u16x8*>(beta + 8 * c8);
-            un_u16x8 o;
+            const u16x8 g = *reinterpret_cast<const u16x8*>(gamma + 8 * c8), b = *reinterpret_cast<const u16x8*>(beta + 8 * c8);
+            u16x8 o;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = un_from_f32<F16>((un_to_f32<F16>(v[i][e]) - mean) * rstd * un_to_f32<F16>(g[e]) + un_to_f32<F16>(b[e]));
-            *reinterpret_cast<un_u16x8*>(yr + 8 * c8) = o;
+            for (int e = 0; e < 8; ++e) o[e] = to_h<F16>((to_f32<F16>(v[i][e]) - mean) * rstd * to_f32<F16>(g[e]) + to_f32<F16>(b[e]));
+            *reinterpret_cast<u16x8*>(yr + 8 * c8) = o;
         }
     }
 }
@@ -85,11 +63,11 @@ __global__ __launch_bounds__(256) void geglu16_kernel(const unsigned short* __re
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
         const long long m = q / d8;
         const int j = 8 * (int)(q - m * d8);
-        const un_u16x8 a = *reinterpret_cast<const un_u16x8*>(x + m * 2 * D + j), g = *reinterpret_cast<const un_u16x8*>(x + m * 2 * D + D + j);
-        un_u16x8 o;
+        const u16x8 a = *reinterpret_cast<const u16x8*>(x + m * 2 * D + j), g = *reinterpret_cast<const u16x8*>(x + m * 2 * D + D + j);
+        u16x8 o;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = un_from_f32<F16>(un_to_f32<F16>(a[e]) * gelu_erf(un_to_f32<F16>(g[e])));
-        *reinterpret_cast<un_u16x8*>(y + m * D + j) = o;
+        for (int e = 0; e < 8; ++e) o[e] = to_h<F16>(to_f32<F16>(a[e]) * gelu_erf(to_f32<F16>(g[e])));
+        *reinterpret_cast<u16x8*>(y + m * D + j) = o;
     }
 }
 
@@ -102,8 +80,8 @@ __global__ __launch_bounds__(256) void concat16_kernel(const unsigned short* __r
         const int k = (int)(q - pq * c8);
         const int n_ = (int)(pq / hw), p = (int)(pq - (long long)n_ * hw), yy = p / W, xx = p - yy * W;
         const long long ipix = ((long long)n_ * Hp + yy + pad) * Wp + xx + pad, opix = ((long long)n_ * Hop + yy + opad) * Wop + xx + opad;
-        const un_u16x8 v = k < ca8 ? *reinterpret_cast<const un_u16x8*>(a + ipix * Ca + 8 * k) : *reinterpret_cast<const un_u16x8*>(b + ipix * Cb + 8 * (k - ca8));
-        *reinterpret_cast<un_u16x8*>(out + opix * (Ca + Cb) + 8 * k) = v;
+        const u16x8 v = k < ca8 ? *reinterpret_cast<const u16x8*>(a + ipix * Ca + 8 * k) : *reinterpret_cast<const u16x8*>(b + ipix * Cb + 8 * (k - ca8));
+        *reinterpret_cast<u16x8*>(out + opix * (Ca + Cb) + 8 * k) = v;
     }
 }
 
@@ -115,7 +93,7 @@ static bool un_a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u
 
 extern "C" int eegclip_layernorm16(const void* x, long long ldx, const void* gamma, const void* beta, void* y, long long ldy, int rows, int C, float eps, int dtype,
                                    void* stream) {
-    if (!x || !gamma || !beta || !y || rows < 1 || C < 8 || C % 8 || C > 64 * 8 * LN16_MAXV || ldx < C || ldy < C || (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16))
+    if (!x || !gamma || !beta || !y || rows < 1 || C < 8 || C % 8 || C > 64 * 8 * LN16_MAXV || ldx < C || ldy < C || !half_dtype_ok(dtype))
         return EEGCLIP_EINVAL;
     if (!un_a16(x) || !un_a16(gamma) || !un_a16(beta) || !un_a16(y) || ldx % 8 || ldy % 8) return EEGCLIP_EALIGN;
     const dim3 g((unsigned)((rows + 3) / 4));
@@ -129,7 +107,7 @@ extern "C" int eegclip_layernorm16(const void* x, long long ldx, const void* gam
 }
 
 extern "C" int eegclip_geglu16(const void* x, void* y, int M, int D, int dtype, void* stream) {
-    if (!x || !y || M < 1 || D < 8 || D % 8 || (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16)) return EEGCLIP_EINVAL;
+    if (!x || !y || M < 1 || D < 8 || D % 8 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
     if (!un_a16(x) || !un_a16(y)) return EEGCLIP_EALIGN;
     long long g = ((long long)M * (D / 8) + 255) / 256;
     if (g > 16384) g = 16384;
@@ -139,8 +117,7 @@ extern "C" int eegclip_geglu16(const void* x, void* y, int M, int D, int dtype, 
 }
 
 extern "C" int eegclip_concat16(const void* a, const void* b, void* out, int N, int H, int W, int pad, int Ca, int Cb, int out_pad, int dtype, void* stream) {
-    if (!a || !b || !out || N < 1 || H < 1 || W < 1 || pad < 0 || pad > 1 || out_pad < 0 || out_pad > 1 || Ca < 8 || Cb < 8 || Ca % 8 || Cb % 8 ||
-        (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16))
+    if (!a || !b || !out || N < 1 || H < 1 || W < 1 || pad < 0 || pad > 1 || out_pad < 0 || out_pad > 1 || Ca < 8 || Cb < 8 || Ca % 8 || Cb % 8 || !half_dtype_ok(dtype))
         return EEGCLIP_EINVAL;
     if (!un_a16(a) || !un_a16(b) || !un_a16(out)) return EEGCLIP_EALIGN;
     long long g = ((long long)N * H * W * ((Ca + Cb) / 8) + 255) / 256;

@@ -12,7 +12,7 @@
 // The few layers with 3 / 4 / 8 channels on one side (conv_in, conv_out, quant convs) run on a direct fp32-accumulate kernel, weights in LDS.
 // GroupNorm: one statistics pass (fp64 partial sums per (image, group), atomics onto 64 addresses per image) and one apply pass (+ SiLU) that writes
 // the next convolution's padded operand.
-#include "eeg_common.h"
+#include "half16.h"
 
 #include <stdlib.h>
 
@@ -27,58 +27,6 @@ constexpr int CV_T = 128, CV_K = 64, CV_NS = CV_NS_BUILD;
 constexpr int CV_ROWB = 2 * CV_K;
 constexpr int CV_TILE_B = CV_T * CV_ROWB;
 constexpr int CV_STAGE_B = 2 * CV_TILE_B;
-
-typedef _Float16 cv_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short cv_u16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short cv_u16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x16 cv_mfma_f16(bf16x8 a, bf16x8 b, f32x16 c) {
-#if defined(EEG_EMU)
-    struct AB { bf16x8 a, b; } in{a, b};
-    auto all = hipemu::wave_allgather(&in, sizeof(in));
-    const int l = hipemu::cur->lane, col = l & 31, hb = 4 * (l >> 5);
-    f32x16 d = c;
-    for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + hb;
-        float acc = c[r];
-        for (int h = 0; h < 2; ++h) {
-            AB ra, rbv;
-            memcpy(&ra, all[row + 32 * h], sizeof(AB));
-            memcpy(&rbv, all[col + 32 * h], sizeof(AB));
-            for (int e = 0; e < 8; ++e) {
-                _Float16 x, y;
-                short sx = ra.a[e], sy = rbv.b[e];
-                memcpy(&x, &sx, 2);
-                memcpy(&y, &sy, 2);
-                acc += (float)x * (float)y;
-            }
-        }
-        d[r] = acc;
-    }
-    return d;
-#else
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cv_f16x8, a), __builtin_bit_cast(cv_f16x8, b), c, 0, 0, 0);
-#endif
-}
-template <bool F16>
-__device__ __forceinline__ float cv_to_f32(unsigned short u) {
-    if (F16) {
-        _Float16 h;
-        memcpy(&h, &u, 2);
-        return (float)h;
-    }
-    return bf16_bits_to_f32(u);
-}
-template <bool F16>
-__device__ __forceinline__ unsigned short cv_from_f32(float v) {
-    if (F16) {
-        const _Float16 h = (_Float16)v;
-        unsigned short u;
-        memcpy(&u, &h, 2);
-        return u;
-    }
-    return f32_to_bf16_bits(v);
-}
 
 struct cv_args {
     const unsigned short* in;          // padded NHWC input, pixel (0, 0) of the padded image 0
@@ -224,30 +172,22 @@ __global__ __launch_bounds__(SPEC ? 512 : 256) void conv16_kernel(const cv_args 
         read_step(0, 0);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-#if !defined(EEG_EMU)
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            sched_fence();
             const int set = s & 1;
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    acc[j][i] = F16 ? cv_mfma_f16(wf[set][j], am[set][i], acc[j][i]) : mfma_bf16_32x32x16(wf[set][j], am[set][i], acc[j][i]);
+                    acc[j][i] = mma32<F16>(wf[set][j], am[set][i], acc[j][i]);
                     const int mi = 4 * s + 2 * j + i;
                     if (j == 0 && i == 0 && s + 1 < 4) {
-#if !defined(EEG_EMU)
-                        __builtin_amdgcn_sched_barrier(0);
-#endif
+                        sched_fence();
                         read_step(s + 1, (s + 1) & 1);
-#if !defined(EEG_EMU)
-                        __builtin_amdgcn_sched_barrier(0);
-#endif
+                        sched_fence();
                     }
                     if (refill && (mi & 1)) issue_one(kt + CV_NS - 1, mi >> 1);
                 }
-#if !defined(EEG_EMU)
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            sched_fence();
         }
         if (refill) advance();
     }
@@ -264,20 +204,20 @@ __global__ __launch_bounds__(SPEC ? 512 : 256) void conv16_kernel(const cv_args 
             for (int eq = 0; eq < 4; ++eq) {
                 const int n = n0 + wn * 64 + 32 * j + 8 * eq + 4 * h;
                 if (EXT && n >= a.Cout) continue;
-                cv_u16x4 bv = cv_u16x4{0, 0, 0, 0}, rv = cv_u16x4{0, 0, 0, 0}, cbv = cv_u16x4{0, 0, 0, 0};
-                if (a.bias) bv = *reinterpret_cast<const cv_u16x4*>(a.bias + n);
-                if (a.R) rv = *reinterpret_cast<const cv_u16x4*>(a.R + opix + n);
-                if (EXT && a.cb) cbv = *reinterpret_cast<const cv_u16x4*>(a.cb + (long long)n_ * a.Cout + n);
-                cv_u16x4 o;
+                u16x4 bv = u16x4{0, 0, 0, 0}, rv = u16x4{0, 0, 0, 0}, cbv = u16x4{0, 0, 0, 0};
+                if (a.bias) bv = *reinterpret_cast<const u16x4*>(a.bias + n);
+                if (a.R) rv = *reinterpret_cast<const u16x4*>(a.R + opix + n);
+                if (EXT && a.cb) cbv = *reinterpret_cast<const u16x4*>(a.cb + (long long)n_ * a.Cout + n);
+                u16x4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float v = acc[j][i][4 * eq + e];
-                    if (a.bias) v += cv_to_f32<F16>(bv[e]);
-                    if (EXT && a.cb) v += cv_to_f32<F16>(cbv[e]);
-                    if (a.R) v += cv_to_f32<F16>(rv[e]);
-                    o[e] = cv_from_f32<F16>(v);
+                    if (a.bias) v += to_f32<F16>(bv[e]);
+                    if (EXT && a.cb) v += to_f32<F16>(cbv[e]);
+                    if (a.R) v += to_f32<F16>(rv[e]);
+                    o[e] = to_h<F16>(v);
                 }
-                *reinterpret_cast<cv_u16x4*>(a.out + opix + n) = o;
+                *reinterpret_cast<u16x4*>(a.out + opix + n) = o;
             }
     }
 }
@@ -295,7 +235,7 @@ __global__ __launch_bounds__(256) void conv_small16_kernel(const cv_args a) {
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
         const int m = (int)(q / a.Cout), co = (int)(q - (long long)m * a.Cout);
         const int n_ = m / hw, rem = m - n_ * hw, y = rem / a.Wo, x = rem - y * a.Wo;
-        float acc = a.bias ? cv_to_f32<F16>(a.bias[co]) : 0.f;
+        float acc = a.bias ? to_f32<F16>(a.bias[co]) : 0.f;
         for (int ky = 0; ky < a.KS; ++ky)
             for (int kx = 0; kx < a.KS; ++kx) {
                 const int sy = a.up ? (((y + ky - 1) >> 1) + 1) : y * a.stride + ky + a.oy;
@@ -304,17 +244,17 @@ __global__ __launch_bounds__(256) void conv_small16_kernel(const cv_args a) {
                 const unsigned short* w = wl + (co * kk + ky * a.KS + kx) * a.Cin;
                 if (vec8) {                                  // 16-byte reads of both operands (conv_out, 128 -> 3 at 1024 x 1024: 6.1 -> ms with 2-byte reads); same summation order
                     for (int ci = 0; ci < a.Cin; ci += 8) {
-                        const cv_u16x8 pv = *reinterpret_cast<const cv_u16x8*>(p + ci), wv = *reinterpret_cast<const cv_u16x8*>(w + ci);
+                        const u16x8 pv = *reinterpret_cast<const u16x8*>(p + ci), wv = *reinterpret_cast<const u16x8*>(w + ci);
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) acc += cv_to_f32<F16>(pv[e]) * cv_to_f32<F16>(wv[e]);
+                        for (int e = 0; e < 8; ++e) acc += to_f32<F16>(pv[e]) * to_f32<F16>(wv[e]);
                     }
                 } else {
-                    for (int ci = 0; ci < a.Cin; ++ci) acc += cv_to_f32<F16>(p[ci]) * cv_to_f32<F16>(w[ci]);
+                    for (int ci = 0; ci < a.Cin; ++ci) acc += to_f32<F16>(p[ci]) * to_f32<F16>(w[ci]);
                 }
             }
         const long long opix = (((long long)n_ * a.Hop + y + a.opad) * a.Wop + x + a.opad) * a.Cout;
-        if (a.R) acc += cv_to_f32<F16>(a.R[opix + co]);
-        a.out[opix + co] = cv_from_f32<F16>(acc);
+        if (a.R) acc += to_f32<F16>(a.R[opix + co]);
+        a.out[opix + co] = to_h<F16>(acc);
     }
 }
 
@@ -337,10 +277,10 @@ __global__ __launch_bounds__(256) void gn_stats16_kernel(const unsigned short* _
 #pragma unroll 4
         for (int p = p0 + pl; p < p1; p += ppi) {
             const int y = p / W, xx = p - y * W;
-            const cv_u16x8 v = *reinterpret_cast<const cv_u16x8*>(x + (((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C + 8 * cc);
+            const u16x8 v = *reinterpret_cast<const u16x8*>(x + (((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C + 8 * cc);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float a = cv_to_f32<F16>(v[e]), b = cv_to_f32<F16>(v[4 + e]);
+                const float a = to_f32<F16>(v[e]), b = to_f32<F16>(v[4 + e]);
                 s0 += a; q0 += a * a;
                 s1 += b; q1 += b * b;
             }
@@ -368,7 +308,7 @@ __global__ __launch_bounds__(256) void gn_stats16_kernel(const unsigned short* _
             float s_ = 0.f, q = 0.f;
             for (int p = p0; p < p1; ++p) {
                 const int y = p / W, xx = p - y * W;
-                const float v = cv_to_f32<F16>(x[(((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C + c]);
+                const float v = to_f32<F16>(x[(((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C + c]);
                 s_ += v;
                 q += v * v;
             }
@@ -400,10 +340,10 @@ __global__ __launch_bounds__(256) void gn_stats16_pairs_kernel(const unsigned sh
         float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
         for (int p = p0 + pl; p < p1; p += ppi) {
             const int y = p / W, xx = p - y * W;
-            const cv_u16x8 v = *reinterpret_cast<const cv_u16x8*>(x + (((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C + 8 * cc);
+            const u16x8 v = *reinterpret_cast<const u16x8*>(x + (((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C + 8 * cc);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float a = cv_to_f32<F16>(v[2 * j]), b = cv_to_f32<F16>(v[2 * j + 1]);
+                const float a = to_f32<F16>(v[2 * j]), b = to_f32<F16>(v[2 * j + 1]);
                 s[j] += a + b;
                 q[j] += a * a + b * b;
             }
@@ -453,16 +393,16 @@ __global__ __launch_bounds__(256) void gn_apply16_kernel(const unsigned short* _
         const int n_ = (int)(pq / hw), p = (int)(pq - (long long)n_ * hw), yy = p / W, xx = p - yy * W;
         const int g = c / cpg;                               // (cpg % 4 == 0: the 4 channels share a group)
         const float mean = tab[2 * (n_ * groups + g)], rstd = tab[2 * (n_ * groups + g) + 1];
-        const cv_u16x4 xv = *reinterpret_cast<const cv_u16x4*>(x + (((long long)n_ * Hp + yy + pad) * Wp + xx + pad) * C + c);
-        const cv_u16x4 gv = *reinterpret_cast<const cv_u16x4*>(gamma + c), bv = *reinterpret_cast<const cv_u16x4*>(beta + c);
-        cv_u16x4 o;
+        const u16x4 xv = *reinterpret_cast<const u16x4*>(x + (((long long)n_ * Hp + yy + pad) * Wp + xx + pad) * C + c);
+        const u16x4 gv = *reinterpret_cast<const u16x4*>(gamma + c), bv = *reinterpret_cast<const u16x4*>(beta + c);
+        u16x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            float v = (cv_to_f32<F16>(xv[e]) - mean) * rstd * cv_to_f32<F16>(gv[e]) + cv_to_f32<F16>(bv[e]);
+            float v = (to_f32<F16>(xv[e]) - mean) * rstd * to_f32<F16>(gv[e]) + to_f32<F16>(bv[e]);
             if (silu_on) v = silu(v);
-            o[e] = cv_from_f32<F16>(v);
+            o[e] = to_h<F16>(v);
         }
-        *reinterpret_cast<cv_u16x4*>(y + (((long long)n_ * Hop + yy + opad) * Wop + xx + opad) * C + c) = o;
+        *reinterpret_cast<u16x4*>(y + (((long long)n_ * Hop + yy + opad) * Wop + xx + opad) * C + c) = o;
     }
 }
 
@@ -495,9 +435,9 @@ __global__ __launch_bounds__(256) void gn_apply16_c2_kernel(const unsigned short
         u16x2 o;
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            float v = (cv_to_f32<F16>(xv[e]) - mean) * rstd * cv_to_f32<F16>(gv[e]) + cv_to_f32<F16>(bv[e]);
+            float v = (to_f32<F16>(xv[e]) - mean) * rstd * to_f32<F16>(gv[e]) + to_f32<F16>(bv[e]);
             if (silu_on) v = silu(v);
-            o[e] = cv_from_f32<F16>(v);
+            o[e] = to_h<F16>(v);
         }
         *reinterpret_cast<u16x2*>(y + (((long long)n_ * Hop + yy + opad) * Wop + xx + opad) * C + c) = o;
     }
@@ -511,18 +451,18 @@ __global__ __launch_bounds__(256) void softmax_rows16_kernel(unsigned short* __r
     unsigned short* row = s + (long long)blockIdx.x * ld;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     float mx = -3.0e38f;
-    for (int c = t; c < cols; c += 256) mx = fmaxf(mx, scale * cv_to_f32<F16>(row[c]));
+    for (int c = t; c < cols; c += 256) mx = fmaxf(mx, scale * to_f32<F16>(row[c]));
     mx = wave_max(mx);
     if (lane == 0) red[w] = mx;
     __syncthreads();
     mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     float sum = 0.f;
-    for (int c = t; c < cols; c += 256) sum += expf(scale * cv_to_f32<F16>(row[c]) - mx);
+    for (int c = t; c < cols; c += 256) sum += expf(scale * to_f32<F16>(row[c]) - mx);
     sum = wave_sum(sum);
     if (lane == 0) red[4 + w] = sum;
     __syncthreads();
     const float inv = 1.0f / ((red[4] + red[5]) + (red[6] + red[7]));
-    for (int c = t; c < cols; c += 256) row[c] = cv_from_f32<F16>(expf(scale * cv_to_f32<F16>(row[c]) - mx) * inv);
+    for (int c = t; c < cols; c += 256) row[c] = to_h<F16>(expf(scale * to_f32<F16>(row[c]) - mx) * inv);
 }
 
 // ---- DiagonalGaussianDistribution.sample of the encoder's moments (padded-free NHWC (N, H, W, 2 L): mean | logvar): z = mean + exp(0.5 clamp(logvar)) noise
@@ -533,11 +473,11 @@ __global__ __launch_bounds__(256) void vae_sample16_kernel(const unsigned short*
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
         const long long p = q / L;
         const int c = (int)(q - p * L);
-        const float mean = cv_to_f32<F16>(mom[p * 2 * L + c]);
-        float lv = cv_to_f32<F16>(mom[p * 2 * L + L + c]);
+        const float mean = to_f32<F16>(mom[p * 2 * L + c]);
+        float lv = to_f32<F16>(mom[p * 2 * L + L + c]);
         lv = fminf(fmaxf(lv, -30.f), 20.f);
-        const float nz = noise ? cv_to_f32<F16>(noise[q]) : 0.f;
-        z[q] = cv_from_f32<F16>(mean + expf(0.5f * lv) * nz);
+        const float nz = noise ? to_f32<F16>(noise[q]) : 0.f;
+        z[q] = to_h<F16>(mean + expf(0.5f * lv) * nz);
     }
 }
 
@@ -547,8 +487,7 @@ using namespace eeg;
 
 static int cv_check(const eegclip_conv16_desc* d) {
     if (!d || !d->in || !d->W || !d->out || d->N < 1 || d->Ho < 1 || d->Wo < 1 || d->Cin < 1 || d->Cout < 1 || (d->KS != 1 && d->KS != 3) ||
-        (d->stride != 1 && d->stride != 2) || d->in_pad < 0 || d->in_pad > 1 || d->out_pad < 0 || d->out_pad > 1 || d->Hi < 1 || d->Wi < 1 ||
-        (d->dtype != EEGCLIP_DT_BF16 && d->dtype != EEGCLIP_DT_F16))
+        (d->stride != 1 && d->stride != 2) || d->in_pad < 0 || d->in_pad > 1 || d->out_pad < 0 || d->out_pad > 1 || d->Hi < 1 || d->Wi < 1 || !half_dtype_ok(d->dtype))
         return EEGCLIP_EINVAL;
     if (d->upsample && (d->KS != 3 || d->stride != 1 || d->in_pad != 1 || d->Ho != 2 * d->Hi || d->Wo != 2 * d->Wi)) return EEGCLIP_EINVAL;
     // every tap of every output pixel must land inside the padded input frame
@@ -616,7 +555,7 @@ extern "C" int eegclip_conv16(const eegclip_conv16_desc* d, void* stream) {
 extern "C" int eegclip_groupnorm16(const void* x, int N, int H, int W, int C, int pad, int groups, const void* gamma, const void* beta, float eps, int silu_on,
                                    void* y, int out_pad, double* sums, int dtype, void* stream) {
     if (!x || !gamma || !beta || !y || !sums || N < 1 || H < 1 || W < 1 || C < 4 || groups < 1 || C % groups || (C / groups) % 2 || pad < 0 || pad > 1 ||
-        out_pad < 0 || out_pad > 1 || (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16))
+        out_pad < 0 || out_pad > 1 || !half_dtype_ok(dtype))
         return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) | reinterpret_cast<uintptr_t>(y) |
          reinterpret_cast<uintptr_t>(sums)) & 7u)
@@ -665,14 +604,14 @@ extern "C" int eegclip_groupnorm16(const void* x, int N, int H, int W, int C, in
 }
 
 extern "C" int eegclip_softmax_rows16(void* s, int rows, int cols, long long ld, float scale, int dtype, void* stream) {
-    if (!s || rows < 1 || cols < 1 || ld < cols || (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16)) return EEGCLIP_EINVAL;
+    if (!s || rows < 1 || cols < 1 || ld < cols || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
     if (dtype == EEGCLIP_DT_F16) EEG_LAUNCH((softmax_rows16_kernel<true>), dim3((unsigned)rows), dim3(256), 8 * sizeof(float), stream, static_cast<unsigned short*>(s), cols, ld, scale);
     else                         EEG_LAUNCH((softmax_rows16_kernel<false>), dim3((unsigned)rows), dim3(256), 8 * sizeof(float), stream, static_cast<unsigned short*>(s), cols, ld, scale);
     return (int)hipGetLastError();
 }
 
 extern "C" int eegclip_vae_sample16(const void* moments, const void* noise, void* z, long long pixels, int latent_channels, int dtype, void* stream) {
-    if (!moments || !z || pixels < 1 || latent_channels < 1 || (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16)) return EEGCLIP_EINVAL;
+    if (!moments || !z || pixels < 1 || latent_channels < 1 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
     long long g = (pixels * latent_channels + 255) / 256;
     if (g > 4096) g = 4096;
     if (dtype == EEGCLIP_DT_F16) EEG_LAUNCH((vae_sample16_kernel<true>), dim3((unsigned)g), dim3(256), 0, stream, static_cast<const unsigned short*>(moments), static_cast<const unsigned short*>(noise), static_cast<unsigned short*>(z), pixels, latent_channels);

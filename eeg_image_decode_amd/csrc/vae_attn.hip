@@ -26,16 +26,13 @@
 // to the I/O dtype before P V; O in fp32, divided by the fp32 row sum once and rounded once.  Tail keys are zero-filled in LDS and masked to -inf
 // (every tile holds at least one real key, so the running maximum is finite from the first tile on); tail query rows are clamped on load and
 // never stored.  No score buffer exists outside the registers and those 16 KB of LDS.
-#include "attn16.h"
+#include "flash16.h"
 
 namespace eeg {
 
 constexpr int VA_KT = 32;        // keys per LDS tile
 constexpr int VA_PAD = 16;       // halfs added to every LDS row (see the header)
 constexpr int VA_XCH = 8 * 2 * 64 * 16;   // bytes of the score exchange: [wave][key tile of 16][lane] f32x4
-
-typedef unsigned int va_u32x4 __attribute__((ext_vector_type(4)));
-typedef short va_s16x4 __attribute__((ext_vector_type(4)));
 
 struct va_args {
     const unsigned short *q, *k, *v;
@@ -44,31 +41,6 @@ struct va_args {
     int T;
     float scale2;   // scale * log2(e)
 };
-
-// ds_read_b64_tr_b16 (csrc/self_attn.hip): per 16-lane group, lane 4q+p addresses row q, columns 4p..4p+3 of a 4 x 16 block; lane i receives
-// column i, row q in element q.  (EXEC must be full: called outside any lane-dependent branch.)
-__device__ __forceinline__ va_s16x4 va_read_tr16(const unsigned short* p) {
-#if defined(EEG_EMU)
-    auto all = hipemu::wave_allgather(&p, sizeof(p));
-    const int l = hipemu::cur->lane, grp = l & ~15, i = l & 15;
-    va_s16x4 r;
-    for (int q = 0; q < 4; ++q) {
-        const unsigned short* src;
-        memcpy(&src, all[grp + 4 * q + (i >> 2)], sizeof(src));
-        r[q] = (short)src[i & 3];
-    }
-    return r;
-#else
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) va_s16x4*)(p));
-#endif
-}
-
-// the instruction scheduler moves nothing across this point
-__device__ __forceinline__ void va_sched_fence() {
-#if !defined(EEG_EMU)
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-}
 
 // 16-byte pieces of one 32 x D tile per thread (512 threads): NC of K, NC of V; piece i = row i / (D / 8), columns 8 (i % (D / 8))
 template <int NC>
@@ -153,10 +125,10 @@ __global__ __launch_bounds__(512) void vae_attn_kernel(const va_args a) {
 #pragma unroll
             for (int p = 0; p < NC; ++p) {
                 if (p + 1 < NC) read_k(p + 1, (p + 1) & 1);
-                va_sched_fence();
+                sched_fence();
 #pragma unroll
                 for (int i = 0; i < 4; ++i) sc[i & 1][i >> 1] = mma<F16>(kf[p & 1][i], bq[2 * p + (i >> 1)], sc[i & 1][i >> 1]);
-                va_sched_fence();
+                sched_fence();
             }
         }
         // the two halves of a query tile meet: [wave][t][lane]
@@ -175,7 +147,7 @@ __global__ __launch_bounds__(512) void vae_attn_kernel(const va_args a) {
         auto read_v = [&](int grp, int set) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const va_s16x4 lo = va_read_tr16(vp + 16 * (4 * grp + i)), hi = va_read_tr16(vp + 16 * (4 * grp + i) + 16 * LD);
+                const s16x4 lo = lds_read_tr16(vp + 16 * (4 * grp + i)), hi = lds_read_tr16(vp + 16 * (4 * grp + i) + 16 * LD);
                 fv[set][i] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             }
         };
@@ -206,15 +178,14 @@ __global__ __launch_bounds__(512) void vae_attn_kernel(const va_args a) {
         l = fmaf(l, alpha, sum);                                           // this lane's keys only: reduced across the 4 groups at the end
 #pragma unroll
         for (int dn = 0; dn < DN; ++dn) acc[dn] *= alpha;
-        const va_u32x4 pw{pack2<F16>(s[0][0], s[0][1]), pack2<F16>(s[0][2], s[0][3]), pack2<F16>(s[1][0], s[1][1]), pack2<F16>(s[1][2], s[1][3])};
-        const bf16x8 pa = __builtin_bit_cast(bf16x8, pw);
+        const bf16x8 pa = flash_pack_p<F16>(s[0], s[1]);
 #pragma unroll
         for (int grp = 0; grp < NC; ++grp) {
             if (grp + 1 < NC) read_v(grp + 1, (grp + 1) & 1);
-            va_sched_fence();
+            sched_fence();
 #pragma unroll
             for (int i = 0; i < 4; ++i) acc[4 * grp + i] = mma<F16>(fv[grp & 1][i], pa, acc[4 * grp + i]);   // O^T[d = DH h + 16dn + 4g + r][query fr]
-            va_sched_fence();
+            sched_fence();
         }
         if (kt + 1 < nkt) {
             unsigned short* Kn = lds + ((kt + 1) & 1) * 2 * TILE;           // last read in tile kt-1, before the previous barrier
@@ -222,18 +193,11 @@ __global__ __launch_bounds__(512) void vae_attn_kernel(const va_args a) {
         }
         __syncthreads();                                                   // (also: the exchange is read before it is written again)
     }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const float inv = 1.0f / l;
-    if (qrow < a.T) {                                                      // O^T tile: 8-byte stores of 4 consecutive d
+    const float inv = flash_row_inv(l);
+    if (qrow < a.T) {
         unsigned short* op = a.out + ((long long)b * a.T + qrow) * a.ldo + DH * h + 4 * g;
 #pragma unroll
-        for (int dn = 0; dn < DN; ++dn) {
-            uint2 w;
-            w.x = pack2<F16>(acc[dn][0] * inv, acc[dn][1] * inv);
-            w.y = pack2<F16>(acc[dn][2] * inv, acc[dn][3] * inv);
-            *reinterpret_cast<uint2*>(op + 16 * dn) = w;
-        }
+        for (int dn = 0; dn < DN; ++dn) flash_store4<F16>(op + 16 * dn, acc[dn], inv);
     }
 }
 
@@ -264,11 +228,11 @@ extern "C" int eegclip_vae_attn_supported(int head_dim, long long ldq, long long
 
 extern "C" int eegclip_vae_attn_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B,
                                     int T, int head_dim, float scale, int dtype, void* stream) {
-    const int rc = eegclip_vae_attn_supported(head_dim, ldq, ldk, ldv, ldo);
+    int rc = eegclip_vae_attn_supported(head_dim, ldq, ldk, ldv, ldo);
     if (rc) return rc;
-    if (!q || !k || !v || !out || B < 1 || T < 1 || B > 65535 || T > 0x7fffff00 || !(scale > 0.f) || !(scale < INFINITY)) return EEGCLIP_EINVAL;
-    if (dtype != EEGCLIP_DT_BF16 && dtype != EEGCLIP_DT_F16) return EEGCLIP_EINVAL;
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) != 0) return EEGCLIP_EALIGN;
+    if (T > 0x7fffff00) return EEGCLIP_EINVAL;
+    rc = flash_args_ok(q, k, v, out, B, T, T, scale, dtype);              // (0 = fine)
+    if (rc) return rc;
     const va_args a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (unsigned short*)out, ldq, ldk, ldv, ldo, T,
                     scale * 1.44269504088896340736f};
     const bool f16 = dtype == EEGCLIP_DT_F16;

@@ -63,22 +63,6 @@ struct wk_table {
     int n;
 };
 
-typedef short wk_s4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ wk_s4 wk_tr_read(const unsigned char* p) {
-#if defined(EEG_EMU)
-    const int lane = hipemu::cur->lane, g = lane >> 4, i = lane & 15;
-    wk_s4 r;
-    for (int j = 0; j < 4; ++j) {
-        const unsigned long long src = hipemu::shfl_idx((unsigned long long)(uintptr_t)p, 16 * g + 4 * j + (i >> 2));
-        r[j] = reinterpret_cast<const short*>((uintptr_t)src)[i & 3];
-    }
-    return r;
-#else
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wk_s4*)(p));
-#endif
-}
-
 // SPEC (round 4): four extra PRODUCER waves issue every LDS-DMA instruction and hold the counted vmcnt waits; the MFMA waves issue no vector-memory
 // instruction in the k-loop.  A wave that does both is in order: it stalls in each LDS-DMA issue while the CU's vector-memory path (~64 B/clk) works
 // through its queue, with its MFMAs unissued behind it -- the two costs add (tools/micro/tile_chain.hip; the InfoNCE tile kernel).
@@ -151,7 +135,7 @@ __global__ __launch_bounds__(128 * WN + (SPEC ? 256 : 0)) void wgrad_tok_kernel(
         for (int nt = 0; nt < NT; ++nt) fob[nt] = 2 * WK_TILE + row * WK_ROWB + (((2 * NT * wn + 2 * nt + cp) ^ sw) << 4) + sub;
     }
     auto frag = [&](const unsigned char* p) {
-        const wk_s4 x = wk_tr_read(p), y = wk_tr_read(p + 16 * WK_ROWB);
+        const s16x4 x = lds_read_tr16(p), y = lds_read_tr16(p + 16 * WK_ROWB);
         return bf16x8{x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
     };
 

@@ -113,6 +113,26 @@ def _row_layout(t, name):
     return t, ld
 
 
+def _flash_operands(name, q, k, v, out, check_shapes):
+    """what self_attention and vae_attention (`name`, for the messages) do with their tensors ahead of the launch, in the order both always had: q, k, v on
+    the GPU in one 16-bit dtype; the caller's own shape rules (`check_shapes()`: rank, head dim, matching and non-empty shapes; it raises); each tensor brought
+    to _row_layout; `out`, shaped like q, allocated, or checked against q when given.  Returns (q, ldq, k, ldk, v, ldv, out, ldo)."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        require_cuda(t, n)
+    if q.dtype not in _CODES or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise EegclipError(f"{name} runs in fp16 or bf16 with one dtype for q, k, v (got {q.dtype}, {k.dtype}, {v.dtype})")
+    check_shapes()
+    q, ldq = _row_layout(q, "q")
+    k, ldk = _row_layout(k, "k")
+    v, ldv = _row_layout(v, "v")
+    if out is None:
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    elif out.shape != q.shape or out.dtype != q.dtype or out.device != q.device:
+        raise EegclipError(f"{name}: out {tuple(out.shape)} {out.dtype} does not match {tuple(q.shape)} {q.dtype}")
+    out, ldo = _row_layout(out, "out")
+    return q, ldq, k, ldk, v, ldv, out, ldo
+
+
 def self_attention(q, k, v, heads, scale=None, out=None, causal=False, prefix=None):
     """softmax(scale * q k^T) v per head of 64 (flash-style, csrc/self_attn.hip: no T x T buffer).  q (B, Tq, C), k / v (B, Tk, C), C = heads * 64,
     fp16 or bf16; the three may be column slices of one fused (B, T, 3C) projection (consumed in place).  scale defaults to 1/8 (diffusers'
@@ -122,30 +142,21 @@ def self_attention(q, k, v, heads, scale=None, out=None, causal=False, prefix=No
         if causal:
             raise EegclipError("self_attention: give `causal` or `prefix`, not both (prefix=0 is the causal mask)")
         causal = True
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        require_cuda(t, n)
-    if q.dtype not in _CODES or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise EegclipError(f"self_attention runs in fp16 or bf16 with one dtype for q, k, v (got {q.dtype}, {k.dtype}, {v.dtype})")
-    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
-        raise EegclipError("self_attention takes (B, T, C) tensors")
-    B, Tq, C = q.shape
-    Tk = k.shape[1]
-    if C != heads * 64:
-        raise EegclipError(f"head_dim must be 64 (C={C}, heads={heads})")
-    if tuple(k.shape) != (B, Tk, C) or tuple(v.shape) != (B, Tk, C):
-        raise EegclipError(f"self_attention: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
-    if B * Tq * Tk == 0:
-        raise EegclipError("self_attention: empty input")
-    if causal and Tq != Tk:
-        raise EegclipError(f"self_attention: the causal form takes Tq == Tk (got {Tq}, {Tk})")
-    q, ldq = _row_layout(q, "q")
-    k, ldk = _row_layout(k, "k")
-    v, ldv = _row_layout(v, "v")
-    if out is None:
-        out = torch.empty(B, Tq, C, dtype=q.dtype, device=q.device)
-    elif tuple(out.shape) != (B, Tq, C) or out.dtype != q.dtype or out.device != q.device:
-        raise EegclipError(f"self_attention: out {tuple(out.shape)} {out.dtype} does not match ({B}, {Tq}, {C}) {q.dtype}")
-    out, ldo = _row_layout(out, "out")
+    def check_shapes():
+        if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+            raise EegclipError("self_attention takes (B, T, C) tensors")
+        B, Tq, C = q.shape
+        Tk = k.shape[1]
+        if C != heads * 64:
+            raise EegclipError(f"head_dim must be 64 (C={C}, heads={heads})")
+        if tuple(k.shape) != (B, Tk, C) or tuple(v.shape) != (B, Tk, C):
+            raise EegclipError(f"self_attention: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
+        if B * Tq * Tk == 0:
+            raise EegclipError("self_attention: empty input")
+        if causal and Tq != Tk:
+            raise EegclipError(f"self_attention: the causal form takes Tq == Tk (got {Tq}, {Tk})")
+    q, ldq, k, ldk, v, ldv, out, ldo = _flash_operands("self_attention", q, k, v, out, check_shapes)
+    (B, Tq, C), Tk = q.shape, k.shape[1]
     scale = 1.0 / math.sqrt(64) if scale is None else float(scale)
     if prefix is not None:
         if not 0 <= int(prefix) <= Tk:
@@ -222,25 +233,16 @@ def vae_attention(q, k, v, scale=None, out=None):
     """softmax(scale * q k^T) v with ONE head of head_dim = C in {128, 256, 384, 512} (flash-style, csrc/vae_attn.hip: no T x T buffer; the VAE's
     mid-block attention).  q, k, v (B, T, C), fp16 or bf16, any T >= 1; the three may be column slices of one packed (B, T, 3C) projection (consumed
     in place).  scale defaults to 1 / sqrt(C).  Returns `out` (B, T, C), which may be given."""
-    for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        require_cuda(t, n)
-    if q.dtype not in _CODES or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise EegclipError(f"vae_attention runs in fp16 or bf16 with one dtype for q, k, v (got {q.dtype}, {k.dtype}, {v.dtype})")
-    if q.dim() != 3 or tuple(k.shape) != tuple(q.shape) or tuple(v.shape) != tuple(q.shape):
-        raise EegclipError(f"vae_attention takes three (B, T, C) tensors of one shape (got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)})")
+    def check_shapes():
+        if q.dim() != 3 or tuple(k.shape) != tuple(q.shape) or tuple(v.shape) != tuple(q.shape):
+            raise EegclipError(f"vae_attention takes three (B, T, C) tensors of one shape (got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)})")
+        B, T, C = q.shape
+        if C % 128 or not 128 <= C <= 512:
+            raise EegclipError(f"vae_attention: head_dim must be 128, 256, 384 or 512 (got {C})")
+        if B * T == 0:
+            raise EegclipError("vae_attention: empty input")
+    q, ldq, k, ldk, v, ldv, out, ldo = _flash_operands("vae_attention", q, k, v, out, check_shapes)
     B, T, C = q.shape
-    if C % 128 or not 128 <= C <= 512:
-        raise EegclipError(f"vae_attention: head_dim must be 128, 256, 384 or 512 (got {C})")
-    if B * T == 0:
-        raise EegclipError("vae_attention: empty input")
-    q, ldq = _row_layout(q, "q")
-    k, ldk = _row_layout(k, "k")
-    v, ldv = _row_layout(v, "v")
-    if out is None:
-        out = torch.empty(B, T, C, dtype=q.dtype, device=q.device)
-    elif tuple(out.shape) != (B, T, C) or out.dtype != q.dtype or out.device != q.device:
-        raise EegclipError(f"vae_attention: out {tuple(out.shape)} {out.dtype} does not match ({B}, {T}, {C}) {q.dtype}")
-    out, ldo = _row_layout(out, "out")
     scale = 1.0 / math.sqrt(C) if scale is None else float(scale)
     check(lib().eegclip_vae_attn_fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, B, T, C, scale, _CODES[q.dtype],
                                      raw_stream()), "vae_attn_fwd")

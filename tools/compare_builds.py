@@ -12,6 +12,10 @@ Cases (the child uses public names only, so it runs under both trees):
   text_encoder_2
   standin_loop     4-step seeded DDIM run of the stand-in pipeline (2 images, guidance 5, 32 x 32 latents), without / with self_attention=True;
   standin_loop_sa  ms = median of 5 further runs, host clock
+  git_caption      a reduced GITCaptioner (2 layers, hidden 128, fp16): forward of 2 x 6 ids over 9 visual tokens and a greedy generate to length 8 -- sha256 over
+                   the logits and the ids; ms = median of 5 further forward + generate runs, host clock
+  low_level        a reduced-width LowLevelEncoder (hidden 128, widths 256-128-64-64-4, bf16, B = 16): forward, then one LowLevelTrainer.step -- sha256 over
+                   the latent and every parameter gradient (the loss is an atomic sum); ms = median of 5 further steps, host clock
 
 Time: the other tree's own runs are the reference.  This tree's median per case must lie within the other tree's [min, max] widened on both sides by
 its spread (max - min); `within_range` records it.  Exit status 1 if a digest differs or a case is outside its range."""
@@ -23,7 +27,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CASES = ("weights", "vae_decode", "unet_512_b1", "unet_1024_b2", "text_encoder", "text_encoder_2", "standin_loop", "standin_loop_sa")
+CASES = ("weights", "vae_decode", "unet_512_b1", "unet_1024_b2", "text_encoder", "text_encoder_2", "standin_loop", "standin_loop_sa", "git_caption",
+         "low_level")
 
 CHILD = r"""
 import hashlib, json, statistics, sys, time
@@ -125,9 +130,34 @@ def standin_loop(sa):
     return {"sha256": digest, "ms": host_ms(run, 5)}
 
 
+def git_caption():
+    from eeg_image_decode_amd.git_caption import GITCaptioner
+    m = GITCaptioner(vocab_size=515, hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256, max_position_embeddings=64,
+                     vision_hidden_size=128, dtype=torch.float16, device="cuda", seed=0)
+    g = torch.Generator().manual_seed(5)
+    vis = torch.randn(2, 9, 128, generator=g).to("cuda", torch.float16)
+    ids = torch.randint(0, 515, (2, 6), generator=g)
+    run = lambda: (m(ids, vis), m.generate(vis, max_length=8))
+    logits, out = run()
+    digest = sha(logits, out)
+    return {"sha256": digest, "ms": host_ms(run, 5)}
+
+
+def low_level():
+    from eeg_image_decode_amd.low_level import LowLevelEncoder, LowLevelTrainer
+    m = LowLevelEncoder(num_channels=2, hidden=128, channels=(256, 128, 64, 64, 4), dtype=torch.bfloat16, device="cuda", seed=1)
+    g = torch.Generator().manual_seed(6)
+    x, target = torch.randn(16, 2, 250, generator=g).cuda(), torch.randn(16, 4, 16, 16, generator=g).cuda()
+    latent = m(x)
+    trainer = LowLevelTrainer(m, lr=1e-3)
+    trainer.step(x, target)
+    digest = sha(latent, *trainer.grads().values())             # not the loss: its workgroups' partial sums are added with atomics, in any order
+    return {"sha256": digest, "ms": host_ms(lambda: trainer.step(x, target), 5)}
+
+
 table = {"weights": weights, "vae_decode": vae_decode, "unet_512_b1": lambda: unet(1, 64), "unet_1024_b2": lambda: unet(2, 128),
          "text_encoder": lambda: text_encoder(0), "text_encoder_2": lambda: text_encoder(1), "standin_loop": lambda: standin_loop(False),
-         "standin_loop_sa": lambda: standin_loop(True)}
+         "standin_loop_sa": lambda: standin_loop(True), "git_caption": git_caption, "low_level": low_level}
 res = {}
 for c in cases:
     if not c.startswith("unet"):
