@@ -153,8 +153,8 @@ class PlanOp(C.Structure):
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_GRAD = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3 = 0, 1
-ABI_VERSION = 18
-DT_BF16, DT_F16 = 0, 1
+ABI_VERSION = 19
+DT_BF16, DT_F16, DT_F32 = 0, 1, 2
 _P, _I, _F, _L, _U64, _U, _D = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_ulonglong, C.c_uint, C.c_double
 
 # name -> argtypes   (restype is always int)
@@ -220,6 +220,8 @@ PROTOTYPES = {
     "eegclip_self_attn_fwd": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P],
     "eegclip_self_attn_causal_fwd": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P],
     "eegclip_self_attn_prefix_fwd": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P],
+    "eegclip_attn80_supported": [_L, _L, _L, _L],
+    "eegclip_attn80_fwd": [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _I, _P],
     "eegclip_gemm16_skinny": [_P, _L, _P, _L, _P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _P],
     "eegclip_decode_attn16": [_P, _L, _P, _L, _L, _P, _L, _I, _I, _I, _I, _F, _I, _P],
     "eegclip_convt16": [C.POINTER(Convt16Desc), _P],
@@ -275,6 +277,8 @@ PROTOTYPES = {
     "eegclip_concat16": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "eegclip_gather_rows16": [_P, _L, _P, _I, _P, _I, _P, _I, _I, _I, _P],
     "eegclip_act16": [_P, _L, _P, _L, _I, _I, _I, _I, _P],
+    "eegclip_patch_rows16": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "eegclip_embed_ln16": [_P, _L, _P, _I, _P, _P, _P, _L, _I, _I, _F, _I, _P],
     "eegclip_head_gemm_slices": [_I, _I, _I],
     "eegclip_head_gemm": [C.POINTER(HeadGemmDesc), _P],
     "eegclip_head_act": [_P, _I, _L, _P, _P, _P, _P, _P, _I, _I, _P],

@@ -72,6 +72,27 @@ class _TextTransformer(nn.Module):
         self.final_layer_norm = nn.LayerNorm(c, eps=eps)
 
 
+def clip_layers(layers, cache, x, B, T, heads, act, causal, head_dim=64):
+    """CLIP's encoder layers over x (B T, C), shared by the text towers (causal, head dim 64) and the vision towers (clip_vision.py: no mask, head dim 64 or
+    80): packed q | k | v in one gemm16 launch (the packed weight in `cache`, a PackedWeights), attention reading that buffer in place, the residuals in the
+    GEMM epilogues.  Returns every layer's output, in order."""
+    C = heads * head_dim
+    ln = lambda t, mod: layernorm16(t, mod.weight, mod.bias, mod.eps)
+    hs = []
+    for i, layer in enumerate(layers):
+        a, mlp = layer.self_attn, layer.mlp
+        ps = [a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.q_proj.bias, a.k_proj.bias, a.v_proj.bias]
+        w, b = cache.get(("qkv", i), ps, lambda: (torch.cat([p.detach() for p in ps[:3]], 0).contiguous(),
+                                                  torch.cat([p.detach() for p in ps[3:]], 0).contiguous()))
+        qkv = linear16(ln(x, layer.layer_norm1), w, b).reshape(B, T, 3 * C)
+        o = self_attention(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], heads, causal=causal, head_dim=head_dim)
+        x = linear16(o.reshape(B * T, C), a.out_proj.weight, a.out_proj.bias, x)
+        f = act16(linear16(ln(x, layer.layer_norm2), mlp.fc1.weight, mlp.fc1.bias), act)
+        x = linear16(f, mlp.fc2.weight, mlp.fc2.bias, x)
+        hs.append(x)
+    return hs
+
+
 class CLIPTextOutput:
     """What diffusers' encode_prompt reads from a transformers output: out[0] (text_embeds with a projection, else last_hidden_state), .hidden_states,
     .last_hidden_state, .pooler_output, .text_embeds.  Indexing skips the fields that are None, as transformers' ModelOutput does."""
@@ -121,11 +142,6 @@ class CLIPTextEncoder(nn.Module):
     def device(self):
         return self.text_model.final_layer_norm.weight.device
 
-    def _qkv(self, i, a):
-        ps = [a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, a.q_proj.bias, a.k_proj.bias, a.v_proj.bias]
-        return self._cache.get(("qkv", i), ps, lambda: (torch.cat([p.detach() for p in ps[:3]], 0).contiguous(),
-                                                          torch.cat([p.detach() for p in ps[3:]], 0).contiguous()))
-
     # ---- layers -------------------------------------------------------------------------------------------------------------------------------------
     def _ids(self, input_ids):
         """ids arrive as host data (a tokenizer's output); a device tensor is copied back: every id is range-checked before a kernel indexes with it"""
@@ -162,16 +178,8 @@ class CLIPTextEncoder(nn.Module):
         dev, act = self.device, ACT_KINDS[cfg.hidden_act]
         ln = lambda x, mod: layernorm16(x, mod.weight, mod.bias, mod.eps)
         x = gather_rows16(emb.token_embedding.weight, ids.reshape(-1).to(dev), B * T, emb.position_embedding.weight, T)
-        hs = [x]
-        for i, layer in enumerate(self.text_model.encoder.layers[:n_run]):
-            a, mlp = layer.self_attn, layer.mlp
-            w, b = self._qkv(i, a)
-            qkv = linear16(ln(x, layer.layer_norm1), w, b).reshape(B, T, 3 * C)
-            o = self_attention(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], heads, causal=True)
-            x = linear16(o.reshape(B * T, C), a.out_proj.weight, a.out_proj.bias, x)
-            f = act16(linear16(ln(x, layer.layer_norm2), mlp.fc1.weight, mlp.fc1.bias), act)
-            x = linear16(f, mlp.fc2.weight, mlp.fc2.bias, x)
-            hs.append(x)
+        hs = [x] + clip_layers(self.text_model.encoder.layers[:n_run], self._cache, x, B, T, heads, act, causal=True)
+        x = hs[-1]
         last = pooled = text_embeds = None
         if n_run == L:
             last2 = ln(x, self.text_model.final_layer_norm)

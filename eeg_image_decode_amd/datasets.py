@@ -15,7 +15,8 @@ the same constructor, attributes, item tuple and index arithmetic, but the whole
     what DataLoader's default collate yields (tensors + lists of str), so train_model / evaluate_model consume it unchanged.
 
 The CLIP text / image encoders (open_clip ViT-H-14) are not part of this path: the cached feature files must exist (the reference writes them
-on first use, :62-74); the `classes` / `pictures` subsets re-encode on every construction (:75-77) and are therefore not offered.
+on first use, :62-74); the `classes` / `pictures` subsets re-encode on every construction (:75-77) and are therefore not offered.  The image rows of
+such a file can be made with `image_features` below (clip_vision.ip_adapter_image_encoder(), the same ViT-H/14 image tower in transformers' layout).
 """
 import json
 import os
@@ -49,6 +50,20 @@ def _listing(directory):
         fp = os.path.join(directory, d)
         images.extend(os.path.join(fp, i) for i in sorted(i for i in os.listdir(fp) if i.lower().endswith((".png", ".jpg", ".jpeg"))))
     return texts, images
+
+
+def image_features(pixel_values, encoder, normalize=True, batch_size=64):
+    """Image batch -> the `img_features` rows the feature cache holds (eegdatasets_leaveone.py ImageEncoder, :108-135: encode_image in batches, each row
+    divided by its norm): fp32 (N, projection_dim) on the encoder's device.  encoder: clip_vision.ip_adapter_image_encoder() with the ViT-H/14 checkpoint
+    loaded; pixel_values (N, 3, 224, 224), resized, cropped and normalised by the caller (reading image files stays
+    there too).  normalize=False keeps the projection's output as it is (the IP-Adapter's image_embeds)."""
+    if encoder.config.projection_dim is None:
+        raise EegclipError("image_features needs an encoder with a visual_projection (clip_vision.ip_adapter_image_encoder())")
+    if batch_size < 1 or len(pixel_values) == 0:
+        raise EegclipError("image_features needs at least one image and a positive batch_size")
+    rows = [encoder(pixel_values[i:i + batch_size]).image_embeds.float() for i in range(0, len(pixel_values), batch_size)]
+    feats = torch.cat(rows, dim=0)
+    return feats / feats.norm(dim=-1, keepdim=True) if normalize else feats
 
 
 class EEGDataset:

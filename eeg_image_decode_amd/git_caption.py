@@ -278,6 +278,12 @@ def caption(visual_features, decoder, model, max_length=20, prompt_ids=None):
     return model.caption(visual_features, decoder, max_length, prompt_ids)
 
 
+def caption_images(pixel_values, decoder, model, tower, max_length=20, prompt_ids=None):
+    """images -> list[str]: GIT's own vision tower (clip_vision.git_vision_tower(), loaded from the same checkpoint's git.image_encoder.* keys) in front of
+    `caption`.  pixel_values (B, 3, 224, 224), preprocessed."""
+    return caption(tower(pixel_values).last_hidden_state, decoder, model, max_length, prompt_ids)
+
+
 # ---------------------------------------------------------------------------------------------------------------------- ids -> text
 class WordPieceDecoder:
     """ids -> text as BERT's uncased tokenizer decodes them (transformers' BertTokenizer.decode(ids, skip_special_tokens=True)), in plain Python: drop

@@ -1,8 +1,8 @@
 """The 16-bit host layer of the generation stack: what sdxl.py (processors, stand-in UNet), sdxl_unet.py, clip_text.py and vae.py share.
 
 * thin wrappers over the 16-bit entry points, free functions taking tensors: linear16 / linear (csrc/gemm16.hip, csrc/vae.hip conv16 as a 1 x 1
-  convolution), linear16_skinny / decode_attention (csrc/caption.hip), self_attention (csrc/self_attn.hip), vae_attention (csrc/vae_attn.hip), cross_attention (csrc/cross_attn.hip), layernorm16 / geglu16 / concat16 (csrc/unet.hip),
-  act16 / gather_rows16 (csrc/clip_text.hip), conv_transpose16 (csrc/convt16.hip).  No library GEMM, no eager fallback: a shape a kernel does not take raises.
+  convolution), linear16_skinny / decode_attention (csrc/caption.hip), self_attention (csrc/self_attn.hip, csrc/attn80.hip), vae_attention (csrc/vae_attn.hip), cross_attention (csrc/cross_attn.hip), layernorm16 / geglu16 / concat16 (csrc/unet.hip),
+  act16 / gather_rows16 (csrc/clip_text.hip), patch_rows16 / embed_ln16 (csrc/clip_vision.hip), conv_transpose16 (csrc/convt16.hip).  No library GEMM, no eager fallback: a shape a kernel does not take raises.
 * PackedWeights: the one cache of repacked weights and the one statement of its key.
 * seeded_parameters: the construction of a module whose nn children hold parameters only and are never called.
 * what both UNets do around their attention stacks: image_embeds_of, text_time_embedding, TokenKV.
@@ -133,22 +133,27 @@ def _flash_operands(name, q, k, v, out, check_shapes):
     return q, ldq, k, ldk, v, ldv, out, ldo
 
 
-def self_attention(q, k, v, heads, scale=None, out=None, causal=False, prefix=None):
-    """softmax(scale * q k^T) v per head of 64 (flash-style, csrc/self_attn.hip: no T x T buffer).  q (B, Tq, C), k / v (B, Tk, C), C = heads * 64,
-    fp16 or bf16; the three may be column slices of one fused (B, T, 3C) projection (consumed in place).  scale defaults to 1/8 (diffusers'
-    attn.scale).  causal: key j reaches query i only if j <= i (CLIP's text encoders; Tq == Tk).  prefix (an int in [0, T]; Tq == Tk): key j reaches
+def self_attention(q, k, v, heads, scale=None, out=None, causal=False, prefix=None, head_dim=64):
+    """softmax(scale * q k^T) v per head of `head_dim` (flash-style: no T x T buffer): 64 on csrc/self_attn.hip, 80 on csrc/attn80.hip (CLIP ViT-H/14; no
+    mask: causal / prefix raise).  q (B, Tq, C), k / v (B, Tk, C), C = heads * head_dim,
+    fp16 or bf16; the three may be column slices of one fused (B, T, 3C) projection (consumed in place).  scale defaults to head_dim ** -0.5 (diffusers'
+    attn.scale: 1/8 at 64).  causal: key j reaches query i only if j <= i (CLIP's text encoders; Tq == Tk).  prefix (an int in [0, T]; Tq == Tk): key j reaches
     query i iff j < max(i + 1, prefix) (GIT's caption decoder: `prefix` image tokens ahead of causal text).  Returns `out` (B, Tq, C), which may be given."""
     if prefix is not None:
         if causal:
             raise EegclipError("self_attention: give `causal` or `prefix`, not both (prefix=0 is the causal mask)")
         causal = True
+    if head_dim not in (64, 80):
+        raise EegclipError(f"self_attention: head_dim must be 64 or 80 (got {head_dim})")
+    if head_dim == 80 and causal:
+        raise EegclipError("self_attention: head_dim 80 (csrc/attn80.hip) has no causal / prefix form")
     def check_shapes():
         if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
             raise EegclipError("self_attention takes (B, T, C) tensors")
         B, Tq, C = q.shape
         Tk = k.shape[1]
-        if C != heads * 64:
-            raise EegclipError(f"head_dim must be 64 (C={C}, heads={heads})")
+        if C != heads * head_dim:
+            raise EegclipError(f"head_dim must be {head_dim} (C={C}, heads={heads})")
         if tuple(k.shape) != (B, Tk, C) or tuple(v.shape) != (B, Tk, C):
             raise EegclipError(f"self_attention: k {tuple(k.shape)} / v {tuple(v.shape)} do not match q {tuple(q.shape)}")
         if B * Tq * Tk == 0:
@@ -157,7 +162,11 @@ def self_attention(q, k, v, heads, scale=None, out=None, causal=False, prefix=No
             raise EegclipError(f"self_attention: the causal form takes Tq == Tk (got {Tq}, {Tk})")
     q, ldq, k, ldk, v, ldv, out, ldo = _flash_operands("self_attention", q, k, v, out, check_shapes)
     (B, Tq, C), Tk = q.shape, k.shape[1]
-    scale = 1.0 / math.sqrt(64) if scale is None else float(scale)
+    scale = 1.0 / math.sqrt(head_dim) if scale is None else float(scale)
+    if head_dim == 80:
+        check(lib().eegclip_attn80_fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, B, Tq, Tk, heads, scale, _CODES[q.dtype],
+                                       raw_stream()), "attn80_fwd")
+        return out
     if prefix is not None:
         if not 0 <= int(prefix) <= Tk:
             raise EegclipError(f"self_attention: prefix must be in [0, {Tk}]; got {prefix}")
@@ -280,6 +289,53 @@ def gather_rows16(table, idx, rows, add=None, add_rows=0):
     check(lib().eegclip_gather_rows16(table.data_ptr(), table.shape[0], idx.data_ptr(), 1, add.data_ptr() if add is not None else None, add_rows,
                                       out.data_ptr(), rows, C, dtype_code(table), raw_stream()), "gather_rows16")
     return out
+
+
+_PIXEL_CODES = {torch.float32: _abi.DT_F32, **_CODES}
+
+
+def patch_rows16(pixels, patch, dtype, scale=None, shift=None):
+    """NCHW pixels (B, 3, H, W) in fp32 / fp16 / bf16 -> the patch convolution's GEMM operand in `dtype`: (B (1 + P), Kpad) rows, Kpad = 3 patch^2 rounded up
+    to a multiple of 64; row b (1 + P) is zero (the class slot), row b (1 + P) + 1 + p is patch p in (c, i, j) order, zero-padded (csrc/clip_vision.hip).
+    scale / shift: fp32 (3) per channel, both or neither: pixel * scale[c] + shift[c] before the one rounding."""
+    require_cuda(pixels, "pixels")
+    dt = dtype_code(dtype)
+    if pixels.dim() != 4 or pixels.shape[1] != 3 or pixels.dtype not in _PIXEL_CODES or pixels.numel() == 0:
+        raise EegclipError(f"patch_rows16 takes (B, 3, H, W) pixels in fp32, fp16 or bf16; got {tuple(pixels.shape)} {pixels.dtype}")
+    B, _, H, W = pixels.shape
+    if patch < 1 or H % patch or W % patch:
+        raise EegclipError(f"patch_rows16: the image ({H} x {W}) is not a whole number of {patch} x {patch} patches")
+    if (scale is None) != (shift is None):
+        raise EegclipError("patch_rows16 takes scale and shift together")
+    for v, n in ((scale, "scale"), (shift, "shift")):
+        if v is not None and (v.dtype != torch.float32 or v.numel() != 3 or not v.is_contiguous() or v.device != pixels.device):
+            raise EegclipError(f"patch_rows16: {n} must be a contiguous fp32 vector of 3 on the pixels' device")
+    pixels = pixels.contiguous()
+    kpad = (3 * patch * patch + 63) // 64 * 64
+    out = torch.empty(B * (1 + (H // patch) * (W // patch)), kpad, dtype=dtype, device=pixels.device)
+    check(lib().eegclip_patch_rows16(pixels.data_ptr(), _PIXEL_CODES[pixels.dtype], scale.data_ptr() if scale is not None else None,
+                                     shift.data_ptr() if shift is not None else None, out.data_ptr(), B, H, W, int(patch), dt, raw_stream()), "patch_rows16")
+    return out
+
+
+def embed_ln16(x, pos, weight, bias, eps):
+    """LayerNorm(x[r] + pos[r % T]) over the rows of x (M, C), pos (T, C) (csrc/clip_vision.hip: the position embedding and pre_layrnorm in one pass)"""
+    require_cuda(x, "x")
+    dt = dtype_code(x)
+    if x.dim() != 2 or x.shape[0] == 0:
+        raise EegclipError(f"embed_ln16 takes (M, C) rows; got {tuple(x.shape)}")
+    M, C = x.shape
+    if x.stride(1) != 1 or x.stride(0) % 8:
+        x = x.contiguous()
+    if pos.dim() != 2 or pos.shape[1] != C or pos.dtype != x.dtype or not pos.is_contiguous() or pos.device != x.device:
+        raise EegclipError(f"embed_ln16: pos {tuple(pos.shape)} {pos.dtype} does not match rows of {C} {x.dtype}")
+    for v, n in ((weight, "weight"), (bias, "bias")):
+        if v.dtype != x.dtype or v.numel() != C or not v.is_contiguous() or v.device != x.device:
+            raise EegclipError(f"embed_ln16: {n} must be a contiguous vector of {C} {x.dtype} on the rows' device")
+    y = torch.empty(M, C, dtype=x.dtype, device=x.device)
+    check(lib().eegclip_embed_ln16(x.data_ptr(), max(x.stride(0), C), pos.data_ptr(), pos.shape[0], weight.data_ptr(), bias.data_ptr(), y.data_ptr(), C, M, C,
+                                   float(eps), dt, raw_stream()), "embed_ln16")
+    return y
 
 
 def concat16(a, b, out):

@@ -499,10 +499,11 @@ class StandInSDXLPipeline:
     reference's constant empty prompt, and any other prompt raises.
     vae: a vae.SDXLShapedVAE (round 6: SDXL's VAE layout on csrc/vae.hip) -- `low_level_image` is then encoded by it
     (custom_pipeline_low_level.py:8-31) and output_type "pt" / "np" decodes the final latents (custom_pipeline.py:421 + image_processor.postprocess:
-    image / 2 + 0.5 clamped to [0, 1]); without one, output_type must be "latent" unless `vae_decode` / `vae_encode` callables are supplied."""
+    image / 2 + 0.5 clamped to [0, 1]); without one, output_type must be "latent" unless `vae_decode` / `vae_encode` callables are supplied.
+    image_encoder: a clip_vision.CLIPVisionEncoder with a projection (ip_adapter_image_encoder()): encode_image and `ip_adapter_image=` then work."""
 
     def __init__(self, unet=None, scheduler=None, device="cuda", dtype=torch.float16, default_sample_size=64, vae_decode=None, vae_encode=None, vae=None,
-                 text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None):
+                 text_encoder=None, text_encoder_2=None, tokenizer=None, tokenizer_2=None, image_encoder=None):
         self.unet = (unet if unet is not None else SDXLShapedUNet(dtype=dtype)).to(device)
         self.scheduler = scheduler if scheduler is not None else EulerAncestralDiscreteScheduler()
         self.device, self.dtype = device, dtype
@@ -524,6 +525,7 @@ class StandInSDXLPipeline:
         self.text_encoder = text_encoder.to(device) if text_encoder is not None else None
         self.text_encoder_2 = text_encoder_2.to(device) if text_encoder_2 is not None else None
         self.tokenizer, self.tokenizer_2 = tokenizer, tokenizer_2
+        self.image_encoder = image_encoder.to(device) if image_encoder is not None else None
         if text_encoder_2 is not None:
             if text_encoder_2.config.projection_dim is None:
                 raise EegclipError("text_encoder_2 must have a text_projection (its out[0] is the pooled text_embeds of the micro-conditioning)")
@@ -597,6 +599,17 @@ class StandInSDXLPipeline:
                 negative_pooled_prompt_embeds = torch.zeros_like(pooled_prompt_embeds)
         return prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds
 
+    def encode_image(self, image, device=None, num_images_per_prompt=1):
+        """StableDiffusionXLPipeline.encode_image (diffusers 0.30.0) without hidden states: pixel_values (B, 3, S, S), preprocessed -> (image_embeds, zeros
+        like them: the negative image embedding)"""
+        if self.image_encoder is None:
+            raise EegclipError("ip_adapter_image needs the CLIP image encoder (absent offline); pass ip_adapter_embeds, as the reference's Generator4Embeds does")
+        embeds = self.image_encoder(image).image_embeds
+        if embeds is None:
+            raise EegclipError("the pipeline's image_encoder has no visual_projection (clip_vision.ip_adapter_image_encoder() has)")
+        embeds = embeds.to(self.dtype).repeat_interleave(num_images_per_prompt, dim=0)
+        return embeds, torch.zeros_like(embeds)
+
     def prepare_latents(self, batch_size, channels, height, width, dtype, device, generator, latents=None):
         shape = (batch_size, channels, height // self.vae_scale_factor, width // self.vae_scale_factor)
         if latents is None:
@@ -640,7 +653,11 @@ def generate_ip_adapter_embeds(self, prompt=None, prompt_2=None, height=None, wi
     micro-conditioning ids -> [negative | positive] batch under classifier-free guidance, zeros as the negative image embedding -> loop:
     scale_model_input, unet, guidance mix, scheduler.step.  The guidance mix and the scheduler update are ONE kernel launch per step."""
     if ip_adapter_image is not None:
-        raise EegclipError("ip_adapter_image needs the CLIP image encoder (absent offline); pass ip_adapter_embeds, as the reference's Generator4Embeds does")
+        if getattr(self, "image_encoder", None) is None:
+            raise EegclipError("ip_adapter_image needs the CLIP image encoder (absent offline); pass ip_adapter_embeds, as the reference's Generator4Embeds does")
+        if ip_adapter_embeds is not None:
+            raise EegclipError("give ip_adapter_image or ip_adapter_embeds, not both")
+        ip_adapter_embeds = self.encode_image(ip_adapter_image)[0]
     if guidance_rescale and guidance_rescale > 0.0:
         raise EegclipError("guidance_rescale is not used on this path (the reference passes 0)")
     height = height or self.default_sample_size * self.vae_scale_factor

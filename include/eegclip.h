@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 18
+#define EEGCLIP_ABI_VERSION 19
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -330,6 +330,7 @@ int eegclip_infonce_loss(const float* X, int n, long long ld, const float* scale
 
 #define EEGCLIP_DT_BF16 0
 #define EEGCLIP_DT_F16 1
+#define EEGCLIP_DT_F32 2   /* input pixels of eegclip_patch_rows16 only: every other `dtype` is one of the two 16-bit codes */
 
 /* ---- 16-bit Linear layers of the SDXL sampling path (row F2: the UNet's to_q / to_k / to_v / to_out and to_k_ip / to_v_ip projections around
  * the cross-attention of Generation/custom_pipeline.py:365-373, which diffusers runs as library GEMMs):
@@ -452,6 +453,17 @@ int eegclip_self_attn_causal_fwd(const void* q, long long ldq, const void* k, lo
  * attention.  Otherwise the causal form's arguments and requirements.  A workgroup's key loop ends at max(its last query + 1, prefix). */
 int eegclip_self_attn_prefix_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B,
                                  int T, int prefix, int heads, int head_dim, float scale, int dtype, void* stream);
+
+/* ---- attention at head dim 80 (csrc/attn80.hip; CLIP ViT-H/14's image tower = the IP-Adapter's models/image_encoder, transformers'
+ * CLIPVisionModelWithProjection: the encoder of the `image_embeds` that Generation/custom_pipeline.py:365-373 conditions on).  (ABI 19.)
+ *   out[b, i, 80h .. 80h+79] = sum_j softmax_j(scale * q[b,i,h] . k[b,j,h]) v[b,j,h]          i < Tq, j < Tk, h < heads          (no mask)
+ * eegclip_self_attn_fwd's contract with C = 80 * heads: rows addressed through ldq / ldk / ldv / ldo (elements), a fused (B*T, 3C) projection consumed in
+ * place; 16-bit I/O (dtype), fp32 scores / softmax / accumulation, no T x T buffer, any Tq, Tk >= 1, scale > 0.  Reads columns [80h, 80h + 80) of a row and
+ * nothing past them; writes only rows < Tq, columns [0, 80 * heads) of out.  Strides multiples of 8 and >= 80 * heads, pointers 16-byte aligned (head h then
+ * starts 160 h bytes into a row: aligned); _supported() checks the strides alone.  Error codes as eegclip_self_attn_fwd, in its order. */
+int eegclip_attn80_supported(long long ldq, long long ldk, long long ldv, long long ldo);
+int eegclip_attn80_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B, int Tq,
+                       int Tk, int heads, float scale, int dtype, void* stream);
 
 /* ---- retrieval readouts.  ATMS_retrieval.py:246 (argmax), :320 (top-5).  ties -> lowest index; out_idx: int64 (rows, k), k <= 8 */
 int eegclip_topk_rows(const float* X, int rows, int cols, long long ld, int k, const float* scale /* device scalar or NULL: rank by scale*x */,
@@ -681,6 +693,20 @@ int eegclip_concat16(const void* a, const void* b, void* out, int N, int H, int 
 int eegclip_gather_rows16(const void* table, long long table_rows, const void* idx, int idx64, const void* add, int add_rows, void* out, int rows, int C,
                           int dtype, void* stream);
 int eegclip_act16(const void* x, long long ldx, void* y, long long ldy, int M, int D, int kind, int dtype, void* stream);
+
+/* ---- the front end of CLIP's vision towers (csrc/clip_vision.hip; transformers' CLIPVisionEmbeddings + pre_layrnorm of CLIPVisionModelWithProjection -- the
+ * IP-Adapter's image encoder, Generation/custom_pipeline.py:365-373 -- and of GIT's git.image_encoder, Generation/modeling_git.py:1970-1973).  (ABI 19.)
+ *   eegclip_patch_rows16  pixels (B, 3, H, W) NCHW of pix_dtype (EEGCLIP_DT_F32 / _F16 / _BF16), H and W multiples of patch -> out: B (1 + P) dense rows of
+ *                         Kpad = 3 patch^2 rounded up to a multiple of 64, P = (H / patch)(W / patch).  Row b (1 + P) is zero (the class slot); row
+ *                         b (1 + P) + 1 + py (W / patch) + px holds pixels [b, c, py patch + i, px patch + j] at column (c patch + i) patch + j, columns >= 3 patch^2
+ *                         zero.  scale / shift: fp32 [3] on the device, both or neither: x * scale[c] + shift[c] in fp32, rounded once; without them a pixel
+ *                         already in `dtype` is copied bit for bit.  A GEMM against patch_embedding.weight flattened to (C, Kpad) follows (eegclip_gemm16).
+ *   eegclip_embed_ln16    y[r] = LayerNorm(x[r] + pos[r % T]) * gamma + beta over rows of C (C % 8 == 0, C <= 4096; row strides ldx / ldy multiples of 8; pos
+ *                         (T, C) dense): the sum and the statistics in fp32, one rounding.  y may be x. */
+int eegclip_patch_rows16(const void* pixels, int pix_dtype, const float* scale, const float* shift, void* out, int B, int H, int W, int patch, int dtype,
+                         void* stream);
+int eegclip_embed_ln16(const void* x, long long ldx, const void* pos, int T, const void* gamma, const void* beta, void* y, long long ldy, int rows, int C, float eps,
+                       int dtype, void* stream);
 
 /* ---- the GIT caption decoder's per-token kernels (csrc/caption.hip; Generation/modeling_git.py: GitForCausalLMClipEmb = transformers' GitForCausalLM with the
  * visual tokens handed in, :1970-1973), 16-bit in (dtype), fp32 arithmetic.  Its prefill runs on eegclip_gemm16, eegclip_layernorm16, eegclip_act16,

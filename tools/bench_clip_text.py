@@ -25,15 +25,16 @@ FAMILIES = (("gemm", ("gemm16",)), ("attention", ("self_attn_kernel",)), ("layer
 SETUP = "setup (torch: weight init, fp16 cast, q|k|v packing, id upload)"
 
 
-def family_of(kernel_name):
-    for fam, keys in FAMILIES:
+def family_of(kernel_name, families=FAMILIES, setup=SETUP):
+    for fam, keys in families:
         if any(k in kernel_name for k in keys):
             return fam
-    return SETUP if ("at::native" in kernel_name or "__amd_rocclr" in kernel_name) else "other"
+    return setup if ("at::native" in kernel_name or "__amd_rocclr" in kernel_name) else "other"
 
 
-def kernel_split(directory):
-    """rocprofv3 --kernel-trace --stats output -> {family: {"calls", "ms", "share_of_forward"}} over the kernels of the traced run"""
+def kernel_split(directory, families=FAMILIES, setup=SETUP):
+    """rocprofv3 --kernel-trace --stats output -> {family: {"calls", "ms", "share_of_forward"}} over the kernels of the traced run.  families: (name, kernel
+    name substrings) pairs; setup: the label of torch's own kernels (building the model), kept out of the shares"""
     fam = {}
     files = glob.glob(os.path.join(directory, "**", "*kernel_stats.csv"), recursive=True)
     if not files:
@@ -41,11 +42,11 @@ def kernel_split(directory):
     for path in files:
         with open(path, newline="") as f:
             for row in csv.DictReader(f):
-                e = fam.setdefault(family_of(row["Name"]), {"calls": 0, "ms": 0.0})
+                e = fam.setdefault(family_of(row["Name"], families, setup), {"calls": 0, "ms": 0.0})
                 e["calls"] += int(row["Calls"])
                 e["ms"] += float(row["TotalDurationNs"]) / 1e6
-    total = sum(e["ms"] for k, e in fam.items() if k != SETUP)          # shares over the forward's own kernels: building the model is not encoding
-    return {k: dict({"calls": e["calls"], "ms": round(e["ms"], 3)}, **({} if k == SETUP else {"share_of_forward": round(e["ms"] / total, 3)}))
+    total = sum(e["ms"] for k, e in fam.items() if k != setup)          # shares over the forward's own kernels: building the model is not encoding
+    return {k: dict({"calls": e["calls"], "ms": round(e["ms"], 3)}, **({} if k == setup else {"share_of_forward": round(e["ms"] / total, 3)}))
             for k, e in sorted(fam.items(), key=lambda kv: -kv[1]["ms"])}
 
 
