@@ -153,8 +153,9 @@ class PlanOp(C.Structure):
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_GRAD = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3 = 0, 1
-ABI_VERSION = 19
+ABI_VERSION = 20
 DT_BF16, DT_F16, DT_F32 = 0, 1, 2
+SRC_U8_HWC, RESIZE_BILINEAR, RESIZE_BICUBIC = 3, 2, 3
 _P, _I, _F, _L, _U64, _U, _D = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_ulonglong, C.c_uint, C.c_double
 
 # name -> argtypes   (restype is always int)
@@ -279,6 +280,8 @@ PROTOTYPES = {
     "eegclip_act16": [_P, _L, _P, _L, _I, _I, _I, _I, _P],
     "eegclip_patch_rows16": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "eegclip_embed_ln16": [_P, _L, _P, _I, _P, _P, _P, _L, _I, _I, _F, _I, _P],
+    "eegclip_resize_coeffs": [_I, _I, _I, _I, _I, _P, _P, _I],
+    "eegclip_resize_crop_normalize": [_P, _I, _F, _F, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _P],
     "eegclip_head_gemm_slices": [_I, _I, _I],
     "eegclip_head_gemm": [C.POINTER(HeadGemmDesc), _P],
     "eegclip_head_act": [_P, _I, _L, _P, _P, _P, _P, _P, _I, _I, _P],

@@ -202,6 +202,12 @@ def sdxl_text_encoder_2(**kw):
     return CLIPTextEncoder(1280, 5120, 32, 20, "gelu", 1280, **kw)
 
 
+def open_clip_vit_h_text_encoder(**kw):
+    """laion/CLIP-ViT-H-14-laion2B-s32B-b79K's text tower with its projection, in transformers' keys (open_clip ViT-H-14's encode_text: the `text_features`
+    of the data sets' feature cache, eegdatasets_leaveone.py:90-106): 1024 wide, 24 layers, 16 heads of 64, gelu, text_embeds (B, 1024)"""
+    return CLIPTextEncoder(1024, 4096, 24, 16, "gelu", 1024, **kw)
+
+
 # ------------------------------------------------------------------------------------------------------------------------------- tokenizer
 def empty_prompt_ids(pad_id=EOS_ID, length=77):
     """what CLIP's tokenizer gives for the reference's constant prompt '': [<|startoftext|>, <|endoftext|>, pad ...] (tokenizer pads with

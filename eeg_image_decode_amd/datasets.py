@@ -15,8 +15,10 @@ the same constructor, attributes, item tuple and index arithmetic, but the whole
     what DataLoader's default collate yields (tensors + lists of str), so train_model / evaluate_model consume it unchanged.
 
 The CLIP text / image encoders (open_clip ViT-H-14) are not part of this path: the cached feature files must exist (the reference writes them
-on first use, :62-74); the `classes` / `pictures` subsets re-encode on every construction (:75-77) and are therefore not offered.  The image rows of
-such a file can be made with `image_features` below (clip_vision.ip_adapter_image_encoder(), the same ViT-H/14 image tower in transformers' layout).
+on first use, :62-74); the `classes` / `pictures` subsets re-encode on every construction (:75-77) and are therefore not offered.  `build_feature_cache`
+below writes such a file from the image directories (PIL decodes on the host, preprocess.open_clip_preprocess resizes on the GPU exactly as PIL would,
+clip_vision.ip_adapter_image_encoder() and clip_text.open_clip_vit_h_text_encoder() are the ViT-H/14 towers in transformers' layout); EEGDataset does it
+on first use when it is given the encoders.
 """
 import json
 import os
@@ -55,8 +57,8 @@ def _listing(directory):
 def image_features(pixel_values, encoder, normalize=True, batch_size=64):
     """Image batch -> the `img_features` rows the feature cache holds (eegdatasets_leaveone.py ImageEncoder, :108-135: encode_image in batches, each row
     divided by its norm): fp32 (N, projection_dim) on the encoder's device.  encoder: clip_vision.ip_adapter_image_encoder() with the ViT-H/14 checkpoint
-    loaded; pixel_values (N, 3, 224, 224), resized, cropped and normalised by the caller (reading image files stays
-    there too).  normalize=False keeps the projection's output as it is (the IP-Adapter's image_embeds)."""
+    loaded; pixel_values (N, 3, 224, 224), resized, cropped and normalised (preprocess.open_clip_preprocess;
+    image_features_from_files below starts from the files).  normalize=False keeps the projection's output as it is (the IP-Adapter's image_embeds)."""
     if encoder.config.projection_dim is None:
         raise EegclipError("image_features needs an encoder with a visual_projection (clip_vision.ip_adapter_image_encoder())")
     if batch_size < 1 or len(pixel_values) == 0:
@@ -66,12 +68,67 @@ def image_features(pixel_values, encoder, normalize=True, batch_size=64):
     return feats / feats.norm(dim=-1, keepdim=True) if normalize else feats
 
 
+def _decode(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"))
+
+
+def image_features_from_files(paths, encoder, batch_size=20, normalize=True):
+    """Image files -> `img_features` rows (eegdatasets_leaveone.py ImageEncoder, :108-135: batches of 20 through preprocess_train and encode_image, each row
+    divided by its norm): PIL decodes on a thread pool of at most 16 workers, preprocess.open_clip_preprocess resizes, crops and normalises on the encoder's
+    device (bit for bit the pixels PIL's resize gives), image_features runs the tower.  fp32 (N, projection_dim)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .preprocess import open_clip_preprocess
+    paths = list(paths)
+    if batch_size < 1 or not paths:
+        raise EegclipError("image_features_from_files needs at least one path and a positive batch_size")
+    size = encoder.config.image_size
+    rows = []
+    with ThreadPoolExecutor(max_workers=min(16, batch_size, len(paths))) as pool:
+        nxt = pool.map(_decode, paths[:batch_size])
+        for i in range(0, len(paths), batch_size):
+            arrays = list(nxt)
+            if i + batch_size < len(paths):
+                nxt = pool.map(_decode, paths[i + batch_size:i + 2 * batch_size])          # (the next batch decodes while this one is on the GPU)
+            px = open_clip_preprocess(arrays, size=size, device=encoder.device)
+            rows.append(image_features(px, encoder, normalize=normalize, batch_size=batch_size))
+    return torch.cat(rows, dim=0)
+
+
+def text_features(texts, text_encoder, tokenizer, batch_size=64):
+    """Class prompts -> `text_features` rows (eegdatasets_leaveone.py Textencoder, :90-106: tokenize, encode_text, each row divided by its norm): fp32
+    (N, projection_dim) on the encoder's device.  text_encoder: clip_text.open_clip_vit_h_text_encoder() with the checkpoint loaded; tokenizer: its
+    clip_text.BPETokenizer."""
+    texts = list(texts)
+    if not texts:
+        raise EegclipError("text_features needs at least one text")
+    if text_encoder.config.projection_dim is None:
+        raise EegclipError("text_features needs an encoder with a text_projection (clip_text.open_clip_vit_h_text_encoder())")
+    rows = [text_encoder(torch.tensor(tokenizer(texts[i:i + batch_size]), dtype=torch.long)).text_embeds.float() for i in range(0, len(texts), batch_size)]
+    feats = torch.cat(rows, dim=0)
+    return feats / feats.norm(dim=-1, keepdim=True)
+
+
+def build_feature_cache(config, train, image_encoder, text_encoder, tokenizer, features_dir="."):
+    """Write <features_dir>/ViT-H-14_features_{train|test}.pt {'text_features', 'img_features'} from the image directories of `config`
+    (eegdatasets_leaveone.py:62-74: what the reference does on first use); returns the path.  Tensors are saved on the host."""
+    texts, images = _listing(config["img_directory_training"] if train else config["img_directory_test"])
+    if not texts or not images:
+        raise EegclipError("build_feature_cache: the image directory lists no class or no image")
+    fn = os.path.join(features_dir, f"{model_type}_features_train.pt" if train else f"{model_type}_features_test.pt")
+    saved = {"text_features": text_features(texts, text_encoder, tokenizer).cpu(), "img_features": image_features_from_files(images, image_encoder).cpu()}
+    torch.save(saved, fn)
+    return fn
+
+
 class EEGDataset:
     """One split (training or test) of one or several THINGS-EEG subjects, resident in HBM; constructor, attributes and item tuple of
-    Retrieval/eegdatasets_leaveone.py:36-375 (keyword-only extras: config, features_dir, device)."""
+    Retrieval/eegdatasets_leaveone.py:36-375 (keyword-only extras: config, features_dir, device; image_encoder, text_encoder, tokenizer: with all three a
+    missing feature file is built first, build_feature_cache, as the reference does on first use)."""
 
     def __init__(self, data_path, exclude_subject=None, subjects=None, train=True, time_window=[0, 1.0], classes=None, pictures=None, val_size=None,
-                 *, config=None, features_dir=".", device="cuda"):
+                 *, config=None, features_dir=".", device="cuda", image_encoder=None, text_encoder=None, tokenizer=None):
         if classes is not None or pictures is not None:
             raise EegclipError("classes / pictures subsets run the CLIP encoders on every construction (eegdatasets_leaveone.py:75-77); "
                                "only the cached-feature configuration (classes=None, pictures=None) is on this path")
@@ -91,6 +148,8 @@ class EEGDataset:
         self.text, self.img = _listing(cfg["img_directory_training"] if train else cfg["img_directory_test"])
         self.data, self.labels = self._stage()
         fn = os.path.join(features_dir, f"{model_type}_features_train.pt" if train else f"{model_type}_features_test.pt")
+        if not os.path.exists(fn) and image_encoder is not None and text_encoder is not None and tokenizer is not None:
+            build_feature_cache(cfg, train, image_encoder, text_encoder, tokenizer, features_dir)
         if not os.path.exists(fn):
             raise EegclipError(f"{fn} not found: the cached CLIP features are an input of this path (the reference creates them with open_clip "
                                "on first use, eegdatasets_leaveone.py:62-74)")

@@ -278,9 +278,14 @@ def caption(visual_features, decoder, model, max_length=20, prompt_ids=None):
     return model.caption(visual_features, decoder, max_length, prompt_ids)
 
 
-def caption_images(pixel_values, decoder, model, tower, max_length=20, prompt_ids=None):
+def caption_images(pixel_values, decoder, model, tower, max_length=20, prompt_ids=None, in_range=None):
     """images -> list[str]: GIT's own vision tower (clip_vision.git_vision_tower(), loaded from the same checkpoint's git.image_encoder.* keys) in front of
-    `caption`.  pixel_values (B, 3, 224, 224), preprocessed."""
+    `caption`.  pixel_values (B, 3, 224, 224), preprocessed; or, as GIT's processor takes them, something that is not a torch.Tensor (a PIL image, a list
+    of them, a uint8 array); or with in_range=(lo, hi) a float (B, 3, H, W) tensor of any size whose values run from lo (black) to hi (white) -- a decoded
+    image straight from the VAE, in_range=(-1, 1).  The last two go through preprocess.clip_image_processor first."""
+    if not isinstance(pixel_values, torch.Tensor) or in_range is not None:
+        from .preprocess import clip_image_processor
+        pixel_values = clip_image_processor(pixel_values, size=tower.config.image_size, device=tower.device, in_range=in_range)
     return caption(tower(pixel_values).last_hidden_state, decoder, model, max_length, prompt_ids)
 
 

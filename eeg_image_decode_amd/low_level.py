@@ -342,9 +342,12 @@ class LowLevelTrainer:
         return self.model
 
 
-def train_low_level(model, loader, epochs, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, vae=None, subject_id=0, loss_scale=1.0, momentum=0.1):
+def train_low_level(model, loader, epochs, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, vae=None, subject_id=0, loss_scale=1.0, momentum=0.1,
+                    image_size=None):
     """The reference's training loop (Generation/train_vae_latent_512_low_level_no_average.py) on one GPU: `loader` yields (eeg, latent) batches, or with
-    `vae` (a vae.SDXLShapedVAE) (eeg, image) batches whose target is vae.encode(image) * vae.scaling_factor, taken without a gradient.  Returns the mean loss
+    `vae` (a vae.SDXLShapedVAE) (eeg, image) batches whose target is vae.encode(image) * vae.scaling_factor, taken without a gradient; with image_size as well, image
+    batches that are not float tensors (uint8 (B, H, W, 3) arrays / tensors, lists of PIL images) go through preprocess.vae_preprocess(size=image_size) first:
+    the script's Resize((512, 512)) + ToTensor, to the VAE's (-1, 1), in the model's dtype.  Returns the mean loss
     of every epoch; the trained values are written into `model` (LowLevelTrainer.sync_model) before it returns.  Data-parallel training is out of scope."""
     tr = LowLevelTrainer(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, loss_scale=loss_scale, momentum=momentum)
     dev = model.device
@@ -352,6 +355,9 @@ def train_low_level(model, loader, epochs, lr=1e-3, betas=(0.9, 0.999), eps=1e-8
     for _ in range(int(epochs)):
         losses = []
         for eeg, target in loader:
+            if vae is not None and image_size is not None and not (isinstance(target, torch.Tensor) and target.is_floating_point()):
+                from .preprocess import vae_preprocess
+                target = vae_preprocess(target, size=int(image_size), dtype=vae.dtype, device=dev)
             eeg, target = eeg.to(dev), target.to(dev)
             if vae is not None:
                 with torch.no_grad():

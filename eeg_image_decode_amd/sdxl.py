@@ -601,9 +601,13 @@ class StandInSDXLPipeline:
 
     def encode_image(self, image, device=None, num_images_per_prompt=1):
         """StableDiffusionXLPipeline.encode_image (diffusers 0.30.0) without hidden states: pixel_values (B, 3, S, S), preprocessed -> (image_embeds, zeros
-        like them: the negative image embedding)"""
+        like them: the negative image embedding).  As in diffusers, an input that is not a torch.Tensor (a PIL image, a list of them, a uint8 array) goes
+        through the feature extractor first: preprocess.clip_image_processor, CLIPImageProcessor's defaults on the GPU."""
         if self.image_encoder is None:
             raise EegclipError("ip_adapter_image needs the CLIP image encoder (absent offline); pass ip_adapter_embeds, as the reference's Generator4Embeds does")
+        if not isinstance(image, torch.Tensor):
+            from .preprocess import clip_image_processor
+            image = clip_image_processor(image, size=self.image_encoder.config.image_size, device=self.image_encoder.device)
         embeds = self.image_encoder(image).image_embeds
         if embeds is None:
             raise EegclipError("the pipeline's image_encoder has no visual_projection (clip_vision.ip_adapter_image_encoder() has)")

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 19
+#define EEGCLIP_ABI_VERSION 20
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -330,7 +330,7 @@ int eegclip_infonce_loss(const float* X, int n, long long ld, const float* scale
 
 #define EEGCLIP_DT_BF16 0
 #define EEGCLIP_DT_F16 1
-#define EEGCLIP_DT_F32 2   /* input pixels of eegclip_patch_rows16 only: every other `dtype` is one of the two 16-bit codes */
+#define EEGCLIP_DT_F32 2   /* input pixels of eegclip_patch_rows16, source and output of eegclip_resize_crop_normalize only: every other `dtype` is a 16-bit code */
 
 /* ---- 16-bit Linear layers of the SDXL sampling path (row F2: the UNet's to_q / to_k / to_v / to_out and to_k_ip / to_v_ip projections around
  * the cross-attention of Generation/custom_pipeline.py:365-373, which diffusers runs as library GEMMs):
@@ -707,6 +707,34 @@ int eegclip_patch_rows16(const void* pixels, int pix_dtype, const float* scale, 
                          void* stream);
 int eegclip_embed_ln16(const void* x, long long ldx, const void* pos, int T, const void* gamma, const void* beta, void* y, long long ldy, int rows, int C, float eps,
                        int dtype, void* stream);
+
+/* ---- image files' bytes -> pixel_values (csrc/image_resize.hip): PIL's 8-bit antialiased resize (Pillow src/libImaging/Resample.c), a crop window and a
+ * per-channel affine in one launch.  Replaces open_clip's preprocess_train in front of the image tower (Retrieval/eegdatasets_leaveone.py:62-74, :108-135:
+ * Resize(224, BICUBIC), CenterCrop(224), ToTensor, Normalize), transformers' CLIPImageProcessor (the pipeline's feature_extractor,
+ * Generation/custom_pipeline.py:365-373, and GIT's processor) and the low-level script's Resize((512, 512)) in front of vae.encode.  Bit-exact with
+ * Image.resize on 8-bit RGB: int32 arithmetic on 22-bit fixed-point coefficients, a rounding to uint8 after each pass.  (ABI 20.)
+ *   eegclip_resize_coeffs  HOST ONLY (host pointers, no stream, nothing enqueued): PIL's precompute_coeffs + normalize_coeffs_8bpc in double for output
+ *                          indices first .. first + count - 1 of an axis resized from in_size to out_size: bounds[i] = (xmin, n), coeffs[i][0 .. ksize - 1] (zero
+ *                          from n on).  filter: EEGCLIP_RESIZE_BILINEAR / _BICUBIC (PIL's codes).  Returns the axis' ksize = 2 ceil(support) + 1 (>= 3; with
+ *                          bounds == coeffs == NULL that is all it does), or EEGCLIP_EINVAL: sizes < 1 or > 2^24, indices outside [0, out_size), an unknown
+ *                          filter, ksize smaller than the axis needs.  Computing the indices of a crop window only is the crop.
+ *   eegclip_resize_crop_normalize  src: B images of H x W, src_kind EEGCLIP_SRC_U8_HWC (uint8 (B, H, W, 3) RGB) or EEGCLIP_DT_F32 / _F16 / _BF16 (planes
+ *                          (B, 3, H, W), quantised on load: p = (uint8) rint(min(max(x a + b, 0), 1) 255) in fp32, unfused, half to even -- diffusers'
+ *                          postprocess(output_type="pil"); a, b are ignored for uint8).  The image is resized to rh x rw; out (B, 3, ch, cw) of `dtype`
+ *                          (EEGCLIP_DT_F32 / _F16 / _BF16) is the window [top, top + ch) x [left, left + cw) of that: q * scale[c] + shift[c] in fp32 (two
+ *                          roundings), rounded once to dtype; scale == shift == NULL: q itself (0..255, exact in all three types).  hbounds / hcoeffs (row
+ *                          stride kh) are eegclip_resize_coeffs(W, rw, left, cw), vbounds / vcoeffs (kv) eegclip_resize_coeffs(H, rh, top, ch), int32 on the device.
+ *                          One workgroup per 16 x 64 output tile per image; the uint8 intermediate of the horizontal pass stays in LDS.  The tile shrinks to
+ *                          fit 64 KiB of LDS; down-scaling by more than 240 (bicubic; 450 bilinear) does not fit the smallest tile: EEGCLIP_EINVAL.  Also
+ *                          EEGCLIP_EINVAL: B < 1 or > 65535, a size or the window < 1, a window outside rh x rw, kh / kv smaller than the axes need, an unknown
+ *                          filter, src_kind or dtype, scale without shift or the reverse.  EEGCLIP_EALIGN: a pointer not aligned to its element. */
+#define EEGCLIP_SRC_U8_HWC 3
+#define EEGCLIP_RESIZE_BILINEAR 2
+#define EEGCLIP_RESIZE_BICUBIC 3
+int eegclip_resize_coeffs(int in_size, int out_size, int first, int count, int filter, int* bounds, int* coeffs, int ksize);
+int eegclip_resize_crop_normalize(const void* src, int src_kind, float a, float b, int B, int H, int W, int rh, int rw, int top, int left, int ch, int cw,
+                                  int filter, const int* hbounds, const int* hcoeffs, int kh, const int* vbounds, const int* vcoeffs, int kv, const float* scale,
+                                  const float* shift, void* out, int dtype, void* stream);
 
 /* ---- the GIT caption decoder's per-token kernels (csrc/caption.hip; Generation/modeling_git.py: GitForCausalLMClipEmb = transformers' GitForCausalLM with the
  * visual tokens handed in, :1970-1973), 16-bit in (dtype), fp32 arithmetic.  Its prefill runs on eegclip_gemm16, eegclip_layernorm16, eegclip_act16,
