@@ -144,20 +144,76 @@ __global__ __launch_bounds__(64) void token_block_pack_kernel(const tb_pack_args
     *reinterpret_cast<tb_u4*>(dst + 512) = ol;
 }
 
+// The B fragments of the first PF k-steps of a GEMM, requested ahead of it (tb_gemm, NEXT) and carried in registers through the epilogue and
+// the barrier of the phase before.
+template <int NT, int PF = 2>
+struct tb_frags {
+    bf16x8 h[PF][NT], l[PF][NT];
+};
+struct tb_none {};
+                                               // "no fragments carried in / none requested for the next GEMM"
+
+// the hi | lo fragment pair of one (n-tile, k-step) -> registers.  Inline asm, so that the request stays where it is written (left to the
+// compiler it sinks towards its use, below stores) -- and the registers are NOT valid until a counted wait has named them (tb_wait_frags).
+template <bool RING = true>
+__device__ __forceinline__ void tb_load_frag(bf16x8& h, bf16x8& l, const bf16x8* q) {
+    if constexpr (!RING) { h = q[0]; l = q[64]; return; }
+#if defined(EEG_EMU)
+    h = q[0];
+    l = q[64];
+#else
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(h) : "v"(q) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:1024" : "=v"(l) : "v"(q) : "memory");
+#endif
+}
+// s_waitcnt vmcnt(N) that names the NT fragment pairs it guards as read-write: no use of them is scheduled above it
+#define TB_WAIT_CASE(N)                                                                                                       \
+    if (n == N) {                                                                                                             \
+        if constexpr (NT == 2) asm volatile("s_waitcnt vmcnt(" #N ")" : "+v"(h[0]), "+v"(l[0]), "+v"(h[1]), "+v"(l[1])::"memory"); \
+        else asm volatile("s_waitcnt vmcnt(" #N ")" : "+v"(h[0]), "+v"(l[0]), "+v"(h[1]), "+v"(l[1]), "+v"(h[NT - 1]), "+v"(l[NT - 1])::"memory"); \
+        return;                                                                                                               \
+    }
+template <int NT>
+__device__ __forceinline__ void tb_wait_frags(int n, bf16x8 (&h)[NT], bf16x8 (&l)[NT]) {
+#if !defined(EEG_EMU)
+    static_assert(NT == 2 || NT == 3, "the wait statements list 2 NT fragment registers");
+    TB_WAIT_CASE(4) TB_WAIT_CASE(6) TB_WAIT_CASE(8) TB_WAIT_CASE(10) TB_WAIT_CASE(12) TB_WAIT_CASE(16) TB_WAIT_CASE(18)
+    n = 0;
+    TB_WAIT_CASE(0)                                              // (any other count: wait for everything)
+#endif
+}
+#undef TB_WAIT_CASE
+// k-step p of the GEMM whose packed tiles start at `wp` -> the carried fragments
+template <int NT, int PF>
+__device__ __forceinline__ void tb_request(const unsigned short* wp, int lane, int p, tb_frags<NT, PF>& c) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) tb_load_frag(c.h[p][j], c.l[p][j], reinterpret_cast<const bf16x8*>(wp + (long long)(j * TB_KS + p) * TB_TILE) + lane);
+}
+// every carried fragment has landed.  Placed BEFORE the first global store of the phase that carries them: stores count in vmcnt and several of
+// them are conditional (dbg & 1, a null xp, valid < 4, tile ranges), so no count after a store could be relied on -- and vmcnt(0) here waits for
+// loads only, requested a k-step or more of MFMAs earlier.
+template <int NT, int PF>
+__device__ __forceinline__ void tb_retire(tb_frags<NT, PF>& c) {
+#pragma unroll
+    for (int p = 0; p < PF; ++p) tb_wait_frags<NT>(0, c.h[p], c.l[p]);
+}
+__device__ __forceinline__ void tb_retire(tb_none&) {}
+
+template <class T> struct tb_frag_nt { static constexpr int nt = 0; };
+template <int NT, int PF> struct tb_frag_nt<tb_frags<NT, PF>> { static constexpr int nt = NT; };
+
 // ---- C[64 x 16 NT] of one wave: A = the AP planes (all 64 rows, K = 256), B = NT packed n-tiles starting at `wp`.
 //      bit j of TM set: tile j is formed TRANSPOSED (MFMA rows = n): lane (fr, g) then holds n = 16 j + 4 g + i of row m = 16 mt + fr;
 //      clear: standard, lane holds rows m = 16 mt + 4 g + i of column n = 16 j + fr.
-#ifndef TB_FWD_RING
-#define TB_FWD_RING false                                   // the forward kernel's GEMMs: compiler-scheduled weight loads (see tb_gemm)
-#endif
-#ifndef TB_QKV_RING
-#define TB_QKV_RING false                                   // ... and its Q | K | V GEMM (NT = 3: 72 ring registers on top of 48 accumulators)
-#endif
-#ifndef TB_BWD_PF
-#define TB_BWD_PF 2                                         // k-steps of weight fragments in flight in the backward kernels' GEMMs
-#endif
-template <int NT, unsigned TM, int PF = 2, bool ZERO = true, bool RING = false>
-__device__ __forceinline__ void tb_gemm(const unsigned char* AP, const unsigned short* wp, int lane, f32x4 (&acc)[4][NT]) {
+//      PRE  = tb_frags<NT, PF>: k-steps 0 .. PF - 1 were requested by the phase before and have landed (tb_retire): the loop begins with MFMAs.
+//      NEXT = tb_frags<.., PF>: the first PF k-steps of the GEMM at `wpn` are requested in the last PF k-steps of this one, where the ring slots
+//             fall free; the caller retires them before its first global store and hands them to that GEMM as PRE.
+template <int NT, unsigned TM, int PF = 2, bool ZERO = true, class PRE = tb_none, class NEXT = tb_none, bool RING = true>
+__device__ __forceinline__ void tb_gemm(const unsigned char* AP, const unsigned short* wp, int lane, f32x4 (&acc)[4][NT], PRE& pre, const unsigned short* wpn,
+                                        NEXT& nxt) {
+    constexpr bool HAS_PRE = tb_frag_nt<PRE>::nt != 0;
+    constexpr int NTN = tb_frag_nt<NEXT>::nt;
+    static_assert(!HAS_PRE || tb_frag_nt<PRE>::nt == NT, "the carried fragments are this GEMM's");
     const int fr = lane & 15, g = lane >> 4;
     if (ZERO) {
 #pragma unroll
@@ -166,67 +222,44 @@ __device__ __forceinline__ void tb_gemm(const unsigned char* AP, const unsigned 
             for (int j = 0; j < NT; ++j) acc[mt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     // the B fragments of k-step ks live in ring slot ks % (PF + 1): PF k-steps of weight loads (L2 round trips) in flight under the MFMAs.
-    // RING: the loads are inline asm with hand-counted waits: left to the compiler, each load is scheduled 4..20 MFMAs ahead of its use (it sinks
+    // The loads are inline asm with hand-counted waits: left to the compiler, each load is scheduled 4..20 MFMAs ahead of its use (it sinks
     // prefetches to shorten live ranges) -- a fraction of the L2 latency -- and every k-step stalls.  Loads retire in order, so "at most
-    // 2 NT x (younger k-steps) operations outstanding" means the fragments of this k-step have landed; the wait names them as read-write so
-    // that no use is scheduled above it (tests/test_asm_rings.py checks the generated code: the compiler must not copy or spill a register whose
-    // load is in flight).  Measured: backward part 0 73 -> 64 us, part 1 37 -> 31 us; the FORWARD kernel, already at the 256-VGPR limit, spills
-    // more with the ring pinned and gets slower (144 -> 151 us train, 107 -> 135 us eval), so it keeps the compiler's schedule.
+    // 2 NT x (younger k-steps) [+ 2 NTN x (requested k-steps of the next GEMM)] operations outstanding" means the fragments of this k-step have
+    // landed; other loads or stores the compiler puts in between only make the count an underestimate of what is younger, which is the safe
+    // side.  The wait names the fragments as read-write so that no use is scheduled above it (tests/test_asm_rings.py checks the generated
+    // code: the compiler must not copy or spill a register whose load is in flight).  Measured: backward part 0 73 -> 64 us, part 1 37 -> 31 us; the
+    // forward 118 -> 111 us with the ring in S1, q | k | v, S4, S7 and the hand-overs between them (profiles/token_block_ring_ab.json).
+    // RING = false leaves the loads to the compiler (S6 of the forward: see there).
     bf16x8 bh[PF + 1][NT], bl[PF + 1][NT];
     auto issue = [&](int ks) {
         const int slot = ks % (PF + 1);
 #pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const bf16x8* q = reinterpret_cast<const bf16x8*>(wp + (long long)(j * TB_KS + ks) * TB_TILE) + lane;
-#if defined(EEG_EMU)
-            bh[slot][j] = q[0];
-            bl[slot][j] = q[64];
-#else
-            if constexpr (RING) {
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(bh[slot][j]) : "v"(q) : "memory");
-                asm volatile("global_load_dwordx4 %0, %1, off offset:1024" : "=v"(bl[slot][j]) : "v"(q) : "memory");
-            } else {
-                bh[slot][j] = q[0];
-                bl[slot][j] = q[64];
-            }
-#endif
-        }
+        for (int j = 0; j < NT; ++j) tb_load_frag<RING>(bh[slot][j], bl[slot][j], reinterpret_cast<const bf16x8*>(wp + (long long)(j * TB_KS + ks) * TB_TILE) + lane);
     };
-    auto landed = [&](int ks) {
-#if !defined(EEG_EMU)
-        if constexpr (!RING) return;
-        static_assert(NT == 2 || NT == 3, "the wait statements list 2 NT fragment registers");
-        const int slot = ks % (PF + 1);
-        const int younger = TB_KS - 1 - ks < PF ? TB_KS - 1 - ks : PF;          // k-steps issued after this one
-#define TB_WAIT(N)                                                                                                                       \
-    do {                                                                                                                                 \
-        if constexpr (NT == 2)                                                                                                           \
-            asm volatile("s_waitcnt vmcnt(" #N ")" : "+v"(bh[slot][0]), "+v"(bl[slot][0]), "+v"(bh[slot][1]), "+v"(bl[slot][1])::"memory"); \
-        else                                                                                                                             \
-            asm volatile("s_waitcnt vmcnt(" #N ")"                                                                                       \
-                         : "+v"(bh[slot][0]), "+v"(bl[slot][0]), "+v"(bh[slot][1]), "+v"(bl[slot][1]), "+v"(bh[slot][NT - 1]), "+v"(bl[slot][NT - 1]) \
-                         :                                                                                                               \
-                         : "memory");                                                                                                    \
-    } while (0)
-        const int n = 2 * NT * younger;
-        if (n == 0) TB_WAIT(0);
-        else if (n == 4) TB_WAIT(4);
-        else if (n == 6) TB_WAIT(6);
-        else if (n == 8) TB_WAIT(8);
-        else if (n == 12) TB_WAIT(12);
-        else if (n == 16) TB_WAIT(16);
-        else if (n == 18) TB_WAIT(18);
-        else TB_WAIT(0);
-#undef TB_WAIT
-#endif
-    };
+    if constexpr (HAS_PRE) {
 #pragma unroll
-    for (int p = 0; p < PF; ++p) issue(p);
+        for (int p = 0; p < PF; ++p)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) { bh[p][j] = pre.h[p][j]; bl[p][j] = pre.l[p][j]; }
+    } else {
+#pragma unroll
+        for (int p = 0; p < PF; ++p) issue(p);
+    }
 #pragma unroll
     for (int ks = 0; ks < TB_KS; ++ks) {
         const int cur = ks % (PF + 1);
-        if (ks + PF < TB_KS) issue(ks + PF);
-        landed(ks);
+        int younger = 0;                                             // operations issued after this k-step's loads, before its wait
+        if (ks + PF < TB_KS) {
+            issue(ks + PF);
+            younger = 2 * NT * PF;
+        } else {
+            younger = 2 * NT * (TB_KS - 1 - ks);
+            if constexpr (NTN != 0) {
+                tb_request(wpn, lane, ks + PF - TB_KS, nxt);
+                younger += 2 * NTN * (ks + PF - TB_KS + 1);
+            }
+        }
+        if (RING && !(HAS_PRE && ks < PF)) tb_wait_frags<NT>(younger, bh[cur], bl[cur]);
         // (pinning the prefetch issue here with sched_barrier(0) measured SLOWER -- 140 vs 120 us per launch: it also stops the scheduler from
         //  running the next k-step's fragment reads under this k-step's MFMAs)
         bf16x8 ah[4], al[4];
@@ -249,6 +282,11 @@ __device__ __forceinline__ void tb_gemm(const unsigned char* AP, const unsigned 
                     else acc[mt][j] = mfma_bf16_16x16x32(aw, bw, acc[mt][j]);
                 }
     }
+}
+template <int NT, unsigned TM, int PF = 2, bool ZERO = true>
+__device__ __forceinline__ void tb_gemm(const unsigned char* AP, const unsigned short* wp, int lane, f32x4 (&acc)[4][NT]) {
+    tb_none none;
+    tb_gemm<NT, TM, PF, ZERO>(AP, wp, lane, acc, none, nullptr, none);
 }
 
 // 4 consecutive-k fp32 -> hi | lo bf16 (8 bytes each) at the same offset of both planes
@@ -389,9 +427,11 @@ struct tb_qkv_variant {
     static constexpr unsigned mask = V == 0 ? 7u : V == 1 ? 7u : V == 2 ? 3u : 0u;      // q and k transposed, v standard
 };
 
-template <int V>
-__device__ __forceinline__ void tb_qkv_pass(const tb_fwd_args& a, const unsigned char* AP, int b, int head, int lane, f32x4 (&acc)[4][3]) {
-    tb_gemm<3, tb_qkv_variant<V>::mask, 2, true, TB_QKV_RING>(AP, a.packed + TB_OFF_QKV + (long long)(head * 12 + 3 * V) * TB_KS * TB_TILE, lane, acc);
+// (k-steps 0, 1 of the pass arrive in `pre`; the first k-steps of the GEMM after it -- the next head pair's pass, or S4 -- leave in `nxt`)
+template <int V, class PRE, class NEXT>
+__device__ __forceinline__ void tb_qkv_pass(const tb_fwd_args& a, const unsigned char* AP, int b, int head, int lane, f32x4 (&acc)[4][3], PRE& pre,
+                                            const unsigned short* wpn, NEXT& nxt) {
+    tb_gemm<3, tb_qkv_variant<V>::mask, 2, true>(AP, a.packed + TB_OFF_QKV + (long long)(head * 12 + 3 * V) * TB_KS * TB_TILE, lane, acc, pre, wpn, nxt);
     // the three tiles' biases first (loads), then every store of the pass: a bias load behind the previous tile's stores would wait for them
     const int fr = lane & 15, g = lane >> 4;
     f32x4 bias[3];
@@ -407,6 +447,7 @@ __device__ __forceinline__ void tb_qkv_pass(const tb_fwd_args& a, const unsigned
             bias[jj] = f32x4{bv, bv, bv, bv};
         }
     }
+    tb_retire(nxt);
 #pragma unroll
     for (int jj = 0; jj < 3; ++jj) {
         const int j = 3 * V + jj, which = j >> 2, tt = j & 3;
@@ -425,6 +466,19 @@ __device__ __forceinline__ void tb_qkv_to_lds(unsigned char* HQ, int lane, const
         const f32x4 v[4] = {acc[0][jj], acc[1][jj], acc[2][jj], acc[3][jj]};
         if ((tb_qkv_variant<V>::mask >> jj) & 1u) tb_qkv_tile_lds<true>(HQ, which, tt, lane, v);
         else tb_qkv_tile_lds<false>(HQ, which, tt, lane, v);
+    }
+}
+
+// q | k | v of one head (a head pair per round: waves 0-3 one head, waves 4-7 the other): this wave's three tiles -> global qkv and the head's planes
+template <class PRE, class NEXT>
+__device__ __forceinline__ void tb_qkv_round(const tb_fwd_args& a, const unsigned char* AP, unsigned char* HQ, int b, int head, int w, int lane, PRE& pre,
+                                             const unsigned short* wpn, NEXT& nxt) {
+    f32x4 cur[4][3];
+    switch (w & 3) {
+        case 0: tb_qkv_pass<0>(a, AP, b, head, lane, cur, pre, wpn, nxt); tb_qkv_to_lds<0>(HQ, lane, cur); break;
+        case 1: tb_qkv_pass<1>(a, AP, b, head, lane, cur, pre, wpn, nxt); tb_qkv_to_lds<1>(HQ, lane, cur); break;
+        case 2: tb_qkv_pass<2>(a, AP, b, head, lane, cur, pre, wpn, nxt); tb_qkv_to_lds<2>(HQ, lane, cur); break;
+        default: tb_qkv_pass<3>(a, AP, b, head, lane, cur, pre, wpn, nxt); tb_qkv_to_lds<3>(HQ, lane, cur); break;
     }
 }
 
@@ -505,14 +559,45 @@ __device__ __forceinline__ void tb_attention(const tb_fwd_args& a, unsigned char
     }
 }
 
+// the 8 rows (of 250 floats, sample base `rows`) that wave w owns in a row pass, as the lane's two column pairs per row (tb_ln_rows: resid_g),
+// requested ahead of the pass with pinned loads like the weight fragments.  A pair outside 0 .. 249 reads the nearest valid one: tb_ln_rows ignores it.
+struct tb_rows {
+    tb_f2 v[8][2];
+};
+__device__ __forceinline__ void tb_request_rows(const float* rows, int w, int lane, tb_rows& o) {
+#pragma unroll
+    for (int rr = 0; rr < 8; ++rr)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int r = 8 * w + rr, cp = 4 * lane - ((r & 1) ? 2 : 0) + 2 * p, cc = cp < 0 ? 0 : cp > TB_D - 2 ? TB_D - 2 : cp;
+            const tb_f2* q = reinterpret_cast<const tb_f2*>(rows + (unsigned)(r * TB_D + cc));
+#if defined(EEG_EMU)
+            o.v[rr][p] = *q;
+#else
+            asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(o.v[rr][p]) : "v"(q) : "memory");
+#endif
+        }
+}
+// (before the first global store of the phase that carries them, like tb_retire)
+__device__ __forceinline__ void tb_retire_rows(tb_rows& o) {
+#if !defined(EEG_EMU)
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        asm volatile("s_waitcnt vmcnt(0)"
+                     : "+v"(o.v[4 * h][0]), "+v"(o.v[4 * h][1]), "+v"(o.v[4 * h + 1][0]), "+v"(o.v[4 * h + 1][1]), "+v"(o.v[4 * h + 2][0]), "+v"(o.v[4 * h + 2][1]),
+                       "+v"(o.v[4 * h + 3][0]), "+v"(o.v[4 * h + 3][1])::"memory");
+#endif
+}
+
 // row pass of the two post-LN sublayer tails: v = resid + dropout(x), y = LN(v) [, y2 = LN(y)].  Wave w owns rows 8 w .. 8 w + 7; a lane owns the 4
 // columns of ONE Philox block of the flat (B, 64, 250) index: c0 = 4 lane - (row odd ? 2 : 0) (row starts are 2 mod 4 for odd rows).
 // x comes from `xs` (an XF-layout LDS image), resid from `resid_lds` (XF layout) or `resid_g` (global rows of 250)
-template <bool TRAIN, bool DOUBLE>
+// `carry`: weight fragments in flight for the GEMM after the pass (or tb_none), retired before the first store
+template <bool TRAIN, bool DOUBLE, class CARRY>      // (resid_rows: the rows of resid_g, already in registers, or null)
 __device__ __forceinline__ void tb_ln_rows(const tb_fwd_args& a, int b, int w, int lane, const unsigned char* xs, const unsigned char* resid_lds,
                                            const float* resid_g, unsigned site, float* r_out, const float* g1, const float* be1, float* y_out, float* mu_out,
                                            float* rs_out, const float* g2, const float* be2, float* y2_out, float* mu2_out, float* rs2_out,
-                                           unsigned char* y_lds /* XF layout or null */, unsigned char* ap /* planes of y or null */) {
+                                           unsigned char* y_lds /* XF layout or null */, unsigned char* ap /* planes of y or null */, CARRY& carry, const tb_rows* resid_rows = nullptr) {
     const long long sb = (long long)b * (TB_L * TB_D);            // uniform: this sample's offset in every (B, 64, 250) tensor
 
     const float ksc = (TRAIN && a.drop_p > 0.f) ? 1.f / (1.f - a.drop_p) : 1.f;
@@ -535,7 +620,10 @@ __device__ __forceinline__ void tb_ln_rows(const tb_fwd_args& a, int b, int w, i
             }
         }
     tb_f2 rg[8][2];
-    if (resid_g) {
+    if (resid_rows) {
+#pragma unroll
+        for (int rr = 0; rr < 8; ++rr) { rg[rr][0] = resid_rows->v[rr][0]; rg[rr][1] = resid_rows->v[rr][1]; }
+    } else if (resid_g) {
 #pragma unroll
         for (int rr = 0; rr < 8; ++rr) {
             const int r = 8 * w + rr, c0 = 4 * lane - ((r & 1) ? 2 : 0);
@@ -546,10 +634,11 @@ __device__ __forceinline__ void tb_ln_rows(const tb_fwd_args& a, int b, int w, i
             }
         }
     }
+    tb_retire(carry);
 #pragma unroll
     for (int rr = 0; rr < 8; ++rr) {
         const int r = 8 * w + rr, c0 = 4 * lane - ((r & 1) ? 2 : 0);
-        const int rbase = r * TB_D;                                 // within the sample: every global access below is (uniform sample base) + 32-bit offset
+        const int rbase = r * TB_D;                            // within the sample: every global access below is (uniform sample base) + 32-bit offset
         float v[4];
         bool ok[2];
         bool keep[4] = {true, true, true, true};
@@ -652,6 +741,14 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_fwd_kernel(const tb
     const int t = threadIdx.x, lane = t & 63, w = wave_uniform(t >> 6), fr = lane & 15, g = lane >> 4;
     const int b = blockIdx.x;
     const float ksc = (TRAIN && a0.drop_p > 0.f) ? 1.f / (1.f - a0.drop_p) : 1.f;
+    // The weight ring does not stop at a phase boundary: the weights of the next GEMM depend on nothing a phase computes, so its first two k-steps
+    // are requested inside the k-loop before it (S7's: behind S6's mid-phase barrier, see there), retired before the phase's first global store and
+    // carried through the epilogue and the barrier (raw_barrier does not drain vmcnt).  A phase that begins behind a barrier otherwise issues its
+    // first loads behind the stores of the phase before, and vmcnt retires in order: it would wait for their HBM round trip.
+    tb_none none;
+    tb_frags<3> cq0, cq1;                                            // q | k | v of the first / second head pair
+    tb_frags<2> c4, c7;                                              // S4, S7
+    tb_rows hrows;                                                   // S5's residual rows of h
 
     tb_stamp(a0, b, t, 0);
     const tb_fwd_args p0 = tb_args_again(a0);                 // this phase's arguments, re-read from the kernel-argument segment (see tb_args_again)
@@ -686,11 +783,13 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_fwd_kernel(const tb
     // ---- S1: value embedding + bias + positional embedding (row = channel), subject token in row 0      (Embed.py:146-160)
     {
         f32x4 acc[4][2];
+        // (the wave's q | k | v tiles of the first head pair: head w >> 2, tiles 3 (w & 3) .. of its 12)
+        const unsigned short* const wq = p1.packed + TB_OFF_QKV + (long long)((w >> 2) * 12 + 3 * (w & 3)) * TB_KS * TB_TILE;
         // (joint-subject model, Embed.py:142-144: the sample's subject picks the Linear -- a workgroup-uniform base, nothing else changes)
         const int vs = p1.embed_subject ? p1.embed_subject[b] : 0;
         const unsigned short* const wv = p1.embed_subject ? p1.packed_embed + (long long)vs * TB_MAT_ELEMS : p1.packed + TB_OFF_V;
         const float* const bvp = p1.bv + (long long)vs * p1.bv_stride;
-        tb_gemm<2, 3u, 2, true, TB_FWD_RING>(AP, wv + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc);
+        tb_gemm<2, 3u, 2, true>(AP, wv + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc, none, wq, cq0);
         const long long id = p1.ids ? p1.ids[b] : 0;
         tb_for_tiles(w, lane, TB_D, acc, [&](int m, int n0, int valid, f32x4& v) {
             f32x4 o;
@@ -703,6 +802,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_fwd_kernel(const tb
             if (valid < 4) { o[2] = 0.f; o[3] = 0.f; }
             *reinterpret_cast<f32x4*>(XF + xf_off(m, n0)) = o;
         });
+        tb_retire(cq0);
         // the EEG sample as token planes (row 0 zero: the subject token has no EEG row) = the X operand of the value embedding's weight gradient
         if (p1.xp && !(p1.dbg & 1u)) tb_planes_out<1>(AP, p1.xp + (long long)b * (2 * TB_AP_PLANE), t);
     }
@@ -744,22 +844,21 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_fwd_kernel(const tb
     {
         const int hip = w >> 2;                                      // head within the pair
         unsigned char* const HQ = lds + TB_AP_BYTES + hip * TB_HQ_BYTES;
-#pragma unroll
-        for (int rd = 0; rd < 2; ++rd) {
-            f32x4 cur[4][3];
-            switch (w & 3) {
-                case 0: tb_qkv_pass<0>(p3, AP, b, 2 * rd + hip, lane, cur); tb_qkv_to_lds<0>(HQ, lane, cur); break;
-                case 1: tb_qkv_pass<1>(p3, AP, b, 2 * rd + hip, lane, cur); tb_qkv_to_lds<1>(HQ, lane, cur); break;
-                case 2: tb_qkv_pass<2>(p3, AP, b, 2 * rd + hip, lane, cur); tb_qkv_to_lds<2>(HQ, lane, cur); break;
-                default: tb_qkv_pass<3>(p3, AP, b, 2 * rd + hip, lane, cur); tb_qkv_to_lds<3>(HQ, lane, cur); break;
-            }
-            if (rd == 1 && !(p3.dbg & 1u)) tb_planes_out<0>(AP, p3.hp + (long long)b * (2 * TB_AP_PLANE), t);      // (the last reader of the h planes has its weights)
-            raw_barrier();
-            tb_stamp(a0, b, t, 10 + 2 * rd);                         // (diagnosis: q | k | v of the head pair done)
-            tb_attention<TRAIN>(p3, HQ, b, 2 * rd + hip, w & 3, lane, ctxr[rd]);
-            raw_barrier();                                           // the pair's planes are dead (and, second round, the h planes too)
-            tb_stamp(a0, b, t, 11 + 2 * rd);                         // (diagnosis: attention of the head pair done)
-        }
+        // (written out per round: the fragments handed on differ in type.  Round 0 requests round 1's first k-steps -- the same tiles, two heads = 24
+        //  tiles on; round 1 requests S4's)
+        tb_qkv_round(p3, AP, HQ, b, hip, w, lane, cq0, p3.packed + TB_OFF_QKV + (long long)((2 + hip) * 12 + 3 * (w & 3)) * TB_KS * TB_TILE, cq1);
+        raw_barrier();
+        tb_stamp(a0, b, t, 10);                                      // (diagnosis: q | k | v of the head pair done)
+        tb_attention<TRAIN>(p3, HQ, b, hip, w & 3, lane, ctxr[0]);
+        raw_barrier();                                               // the pair's planes are dead
+        tb_stamp(a0, b, t, 11);                                      // (diagnosis: attention of the head pair done)
+        tb_qkv_round(p3, AP, HQ, b, 2 + hip, w, lane, cq1, p3.packed + TB_OFF_O + (long long)(2 * w) * TB_KS * TB_TILE, c4);
+        if (!(p3.dbg & 1u)) tb_planes_out<0>(AP, p3.hp + (long long)b * (2 * TB_AP_PLANE), t);      // (the last reader of the h planes has its weights)
+        raw_barrier();
+        tb_stamp(a0, b, t, 12);
+        tb_attention<TRAIN>(p3, HQ, b, 2 + hip, w & 3, lane, ctxr[1]);
+        raw_barrier();                                               // the pair's planes are dead, and the h planes too
+        tb_stamp(a0, b, t, 13);
         // context -> A planes with 64 columns per head (dims 62, 63 are exact zeros); S4 copies the planes to HBM
 #pragma unroll
         for (int rd = 0; rd < 2; ++rd) {
@@ -779,7 +878,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_fwd_kernel(const tb
     // ---- S4: output projection + bias -> XF      (SelfAttention_Family.py:213)
     {
         f32x4 acc[4][2];
-        tb_gemm<2, 3u, 2, true, TB_FWD_RING>(AP, p4.packed + TB_OFF_O + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc);
+        tb_gemm<2, 3u, 2, true>(AP, p4.packed + TB_OFF_O + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc, c4, nullptr, none);
         tb_for_tiles(w, lane, TB_D, acc, [&](int m, int n0, int valid, f32x4& v) {
             const f32x4 bias = tb_ld4(p4.bo + n0, valid);
             f32x4 o;
@@ -787,14 +886,19 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_fwd_kernel(const tb
             for (int i = 0; i < 4; ++i) o[i] = i < valid ? v[i] + bias[i] : 0.f;
             *reinterpret_cast<f32x4*>(XF + xf_off(m, n0)) = o;
         });
+        // S5's residual rows of h, requested ahead of the ctx plane stores (a load behind them would wait for their round trip) -- so the barrier
+        // below need not drain vmcnt.  h is in L2 by now: every wave's S2 stores of h are older than its q | k | v weight loads of k-steps 2 .. 7,
+        // the wave has waited for those (the ring's counted waits: retirement is in order, on every path through S3), and four barriers lie between.
+        tb_request_rows(p4.h + (long long)b * (TB_L * TB_D), w, lane, hrows);
+        tb_retire_rows(hrows);
         if (!(p4.dbg & 1u)) tb_planes_out<0>(AP, p4.ctxp + (long long)b * (2 * TB_AP_PLANE), t);      // ctx planes (channel 255 = dim 63 of head 3: the ones column)
     }
-    __syncthreads();                                                 // (the one barrier that also waits for global stores: S5 re-reads h)
+    raw_barrier();
     tb_stamp(a0, b, t, 5);
     const tb_fwd_args p5 = tb_args_again(a0);                 // this phase's arguments, re-read from the kernel-argument segment (see tb_args_again)
     // ---- S5: r1 = h + dropout(attention output), n1 = LayerNorm1(r1); n1 stays in XF (FFN residual) and goes to the A planes
     tb_ln_rows<TRAIN, false>(p5, b, w, lane, XF, nullptr, p5.h, p5.site_attn_out, p5.r1, p5.ln1_g, p5.ln1_b, nullptr, p5.mu1, p5.rs1, nullptr, nullptr, nullptr, nullptr,
-                             nullptr, XF, AP);
+                             nullptr, XF, AP, none, &hrows);
     raw_barrier();
 
     tb_stamp(a0, b, t, 6);
@@ -802,7 +906,9 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_fwd_kernel(const tb
     // ---- S6: FFN 1 + bias -> f1 (pre-activation, kept for the backward), g1 = dropout(gelu(f1))      (Transformer_EncDec.py:48)
     {
         f32x4 acc[4][2];
-        tb_gemm<2, 3u, 2, true, TB_FWD_RING>(AP, p6.packed + TB_OFF_1 + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc);
+        // (the one GEMM on the compiler's schedule, RING = false: pinned, the kernel spills -- the GELU / Philox epilogue below is its register peak, and what
+        //  is spilled are kernel-long values that every row pass then reloads.  Register counts tried: CHANGELOG)
+        tb_gemm<2, 3u, 2, true, tb_none, tb_none, false>(AP, p6.packed + TB_OFF_1 + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc, none, nullptr, none);
         f32x4 bias1[2];                                              // (loads before the first store: see tb_ln_rows)
 #pragma unroll
         for (int j = 0; j < 2; ++j) bias1[j] = *reinterpret_cast<const f32x4*>(p6.b1 + 32 * w + 16 * j + 4 * g);
@@ -825,6 +931,8 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_fwd_kernel(const tb
         });
         if (!(p6.dbg & 1u)) tb_planes_out<0>(AP, p6.n1p + (long long)b * (2 * TB_AP_PLANE), t);
         raw_barrier();                                               // every wave is done with the n1 planes
+#pragma unroll
+        for (int p = 0; p < 2; ++p) tb_request(p6.packed + TB_OFF_2 + (long long)(2 * w) * TB_KS * TB_TILE, lane, p, c7);
         tb_for_tiles(w, lane, TB_FF, acc, [&](int m, int n0, int valid, f32x4& v) {
             tb_store_planes4(AP, TB_AP_PLANE, ap_off(m, n0), v[0], v[1], v[2], v[3]);
         });
@@ -836,7 +944,8 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_fwd_kernel(const tb
     // ---- S7: FFN 2 + bias; the result replaces the (dead) g1 planes as an fp32 image      (Transformer_EncDec.py:49)
     {
         f32x4 acc[4][2];
-        tb_gemm<2, 3u, 2, true, TB_FWD_RING>(AP, p7.packed + TB_OFF_2 + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc);
+        tb_retire(c7);
+        tb_gemm<2, 3u, 2, true>(AP, p7.packed + TB_OFF_2 + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc, c7, nullptr, none);
         f32x4 bias2[2];                                              // (loads before the stores below)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -864,7 +973,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_fwd_kernel(const tb
     const tb_fwd_args p8 = tb_args_again(a0);                 // this phase's arguments, re-read from the kernel-argument segment (see tb_args_again)
     // ---- S8: r2 = n1 + dropout(FFN output), n2 = LayerNorm2(r2), n3 = final LayerNorm(n2)      (Transformer_EncDec.py:51,77-78)
     tb_ln_rows<TRAIN, true>(p8, b, w, lane, AP, XF, nullptr, p8.site_ffn_out, p8.r2, p8.ln2_g, p8.ln2_b, p8.n2, p8.mu2, p8.rs2, p8.ln3_g, p8.ln3_b, p8.n3, p8.mu3, p8.rs3,
-                            nullptr, nullptr);
+                            nullptr, nullptr, none);
     tb_stamp(a0, b, t, 9);
     // ---- S9 (training plans): the conv stack's BatchNorm1 batch sums of this sample.  The statistics need y1 of EVERY sample before cstack_fwd can normalise
     // one, so they were a launch of their own (cstack_stats1: 18 - 20 us, 16 MB of token rows read back from HBM); here the workgroup goes on with its own
@@ -896,6 +1005,15 @@ struct tb_bwd_args {
     unsigned site_embed, site_attn_out, site_ffn_act, site_ffn_out;
 };
 
+// the value lane `src` (a compile-time constant after unrolling) holds, in every lane: a scalar register
+__device__ __forceinline__ float tb_lane_value(float v, int src) {
+#if defined(EEG_EMU)
+    return __shfl(v, src, 64);
+#else
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
+#endif
+}
+
 // LayerNorm backward of one row slice held by a lane (4 columns, ok[p] per pair): dx = rs (g - mean(g) - xh mean(g xh)), g = dy gamma
 __device__ __forceinline__ void tb_ln_bwd_row(const float (&dy)[4], const float (&x)[4], const float (&gam)[4], const bool (&ok)[2], float mu, float rs,
                                               float (&dx)[4], float (&pg)[4], float (&pb)[4]) {
@@ -917,8 +1035,9 @@ __device__ __forceinline__ void tb_ln_bwd_row(const float (&dy)[4], const float 
 
 // the per-lane partial sums of NV parameter-gradient vectors (even rows own columns 4 lane.., odd rows 4 lane - 2..) -> one row per vector and
 // sample in `out` ([NV][256]); `slab` = 8 x NV x 256 floats of LDS scratch
-template <int NV>
-__device__ __forceinline__ void tb_reduce_partials(float* slab, int w, int lane, int t, const float (&pe)[NV][4], const float (&po)[NV][4], float* out) {
+// (`carry`: weight fragments in flight for the GEMM after the pass, or tb_none: retired before the rows are stored)
+template <int NV, class CARRY>
+__device__ __forceinline__ void tb_reduce_partials(float* slab, int w, int lane, int t, const float (&pe)[NV][4], const float (&po)[NV][4], float* out, CARRY& carry) {
     float* mine = slab + w * (NV * 256);
 #pragma unroll
     for (int v = 0; v < NV; ++v) *reinterpret_cast<f32x4*>(mine + v * 256 + 4 * lane) = f32x4{pe[v][0], pe[v][1], pe[v][2], pe[v][3]};
@@ -931,6 +1050,7 @@ __device__ __forceinline__ void tb_reduce_partials(float* slab, int w, int lane,
             if (c >= 0) mine[v * 256 + c] += po[v][e];              // (a lane's four odd-row columns belong to no other lane's odd-row set)
         }
     raw_barrier();
+    tb_retire(carry);
     for (int i = t; i < NV * 256; i += TB_THREADS) {
         float sum = 0.f;
 #pragma unroll
@@ -948,7 +1068,9 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
     const int t = threadIdx.x, lane = t & 63, w = wave_uniform(t >> 6);
     const int b = blockIdx.x;
     const float ksc = (TRAIN && a0.drop_p > 0.f) ? 1.f / (1.f - a0.drop_p) : 1.f;
-    float* const part = a0.partials + (long long)b * (6 * 256);
+    // (the weight ring across phase boundaries: see token_block_fwd_kernel)
+    tb_none none;
+    tb_frags<2> c2, c3, c5;                                          // the first k-steps of T2, T3, T5
 
     const tb_bwd_args q1 = tb_args_again(a0);                 // (see tb_args_again)
     // ---- T1: final LayerNorm' and LayerNorm2' chained per row in registers; df2 = dropout'(dr2) -> A planes (T2 copies them to HBM), dr2 -> XF
@@ -970,6 +1092,13 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
                 pg2[par][p] = okc ? *reinterpret_cast<const tb_f2*>(q1.ln2_g + cp) : tb_f2{0.f, 0.f};
                 pb2[par][p] = (okc && !q1.n2) ? *reinterpret_cast<const tb_f2*>(q1.ln2_b + cp) : tb_f2{0.f, 0.f};
             }
+        // the row statistics of the wave's 8 rows as ONE vector load (lane 8 k + rr: statistic k = mu3, rs3, mu2, rs2 of row rr), read back per row with
+        // v_readlane, instead of 32 scalar loads through four base pointers that stay live across the row loop: the loop ran out of scalar registers
+        float stat = 0.f;
+        if (lane < 32) {
+            const float* const sp = (lane >> 3) == 0 ? q1.mu3 : (lane >> 3) == 1 ? q1.rs3 : (lane >> 3) == 2 ? q1.mu2 : q1.rs2;
+            stat = sp[(long long)b * TB_L + 8 * w + (lane & 7)];
+        }
         tb_f2 in_dy[8][2], in_r2[8][2], in_n2[8][2];
 #pragma unroll
         for (int rr = 0; rr < 8; ++rr)
@@ -989,6 +1118,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
             const long long row = (long long)b * TB_L + r, rbase = row * TB_D;
             float dy[4], x3[4], x2[4], g3[4], g2[4];
             bool ok[2];
+            const float mu3 = tb_lane_value(stat, rr), rs3 = tb_lane_value(stat, 8 + rr), mu2 = tb_lane_value(stat, 16 + rr), rs2 = tb_lane_value(stat, 24 + rr);
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
                 const int cp = c0 + 2 * p;
@@ -998,7 +1128,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
                 if (ok[p] && !q1.n2) {
                     // n2 = LayerNorm2(r2) is re-evaluated from r2 and the row statistics (the forward did not store it: 16 MB per step less each way)
                     const tb_f2 bb = pb2[rr & 1][p];
-                    const float mu = q1.mu2[row], rs = q1.rs2[row];
+                    const float mu = mu2, rs = rs2;
                     v1 = tb_f2{(v2[0] - mu) * rs * v4[0] + bb[0], (v2[1] - mu) * rs * v4[1] + bb[1]};
                 }
 #pragma unroll
@@ -1006,11 +1136,11 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
             }
             float dn2[4], dr2[4];
             if (rr & 1) {
-                tb_ln_bwd_row(dy, x3, g3, ok, q1.mu3[row], q1.rs3[row], dn2, po[0], po[1]);
-                tb_ln_bwd_row(dn2, x2, g2, ok, q1.mu2[row], q1.rs2[row], dr2, po[2], po[3]);
+                tb_ln_bwd_row(dy, x3, g3, ok, mu3, rs3, dn2, po[0], po[1]);
+                tb_ln_bwd_row(dn2, x2, g2, ok, mu2, rs2, dr2, po[2], po[3]);
             } else {
-                tb_ln_bwd_row(dy, x3, g3, ok, q1.mu3[row], q1.rs3[row], dn2, pe[0], pe[1]);
-                tb_ln_bwd_row(dn2, x2, g2, ok, q1.mu2[row], q1.rs2[row], dr2, pe[2], pe[3]);
+                tb_ln_bwd_row(dy, x3, g3, ok, mu3, rs3, dn2, pe[0], pe[1]);
+                tb_ln_bwd_row(dn2, x2, g2, ok, mu2, rs2, dr2, pe[2], pe[3]);
             }
             bool keep[4] = {true, true, true, true};
             if (TRAIN && q1.drop_p > 0.f && c0 < TB_D) dropout_keep4(q1.seed, q1.site_ffn_out, (unsigned long long)(rbase + c0), q1.drop_p, keep);
@@ -1024,7 +1154,10 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
             }
             if ((rr & 1) && lane == 63) tb_store_planes2(AP, TB_AP_PLANE, ap_off(r, 254), 0.f, 0.f);
         }
-        tb_reduce_partials<4>(SC, w, lane, t, pe, po, part);
+        // (T2's first k-steps: requested behind the row loop, whose registers they would crowd, and ahead of the partial rows' stores)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) tb_request(q1.packed + TB_OFF_2T + (long long)(2 * w) * TB_KS * TB_TILE, lane, p, c2);
+        tb_reduce_partials<4>(SC, w, lane, t, pe, po, tb_args_again(a0).partials + (long long)b * (6 * 256), c2);      // (read here: two scalar registers less through the row loop)
     }
     raw_barrier();
 
@@ -1032,13 +1165,14 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
     // ---- T2: dg1 = df2 W2, then the FFN activation's dropout' and gelu' (pre-activation f1 from HBM): df1 -> A planes (T3 copies them to HBM)
     {
         f32x4 acc[4][2];
-        tb_gemm<2, 3u, TB_BWD_PF, true, true>(AP, q2.packed + TB_OFF_2T + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc);
+        tb_gemm<2, 3u, 2, true>(AP, q2.packed + TB_OFF_2T + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc, c2, q2.packed + TB_OFF_1T + (long long)(2 * w) * TB_KS * TB_TILE, c3);
         f32x4 fpre[4][2];                                            // the pre-activations of this lane's 8 groups: loaded before the first store
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
                 fpre[mt][j] = *reinterpret_cast<const f32x4*>(q2.f1 + (long long)b * (TB_L * TB_FF) + (unsigned)((16 * mt + (lane & 15)) * TB_FF + 32 * w + 16 * j + 4 * (lane >> 4)));
+        tb_retire(c3);
         tb_planes_out<64>(AP, q2.df2p + (long long)b * (2 * TB_AP_PLANE), t);      // df2 planes (bias gradient: all-ones fragment in the GEMM, g1 has 256 channels)
         tb_for_tiles(w, lane, TB_FF, acc, [&](int m, int n0, int valid, f32x4& v) {
             const long long ob = (long long)b * (TB_L * TB_FF);
@@ -1063,7 +1197,8 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
     // ---- T3: dn1 = dr2 + df1 W1 (in place in XF)
     {
         f32x4 acc[4][2];
-        tb_gemm<2, 3u, TB_BWD_PF, true, true>(AP, q3.packed + TB_OFF_1T + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc);
+        // (T4 is a row pass: T5's first k-steps are requested here, ahead of the dg1 plane stores, and ride through it)
+        tb_gemm<2, 3u, 2, true>(AP, q3.packed + TB_OFF_1T + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc, c3, q3.packed + TB_OFF_OT + (long long)(2 * w) * TB_KS * TB_TILE, c5);
         tb_for_tiles(w, lane, TB_D, acc, [&](int m, int n0, int valid, f32x4& v) {
             f32x4* p = reinterpret_cast<f32x4*>(XF + xf_off(m, n0));
             f32x4 o = *p;
@@ -1071,6 +1206,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
             for (int i = 0; i < 4; ++i) o[i] = i < valid ? o[i] + v[i] : 0.f;
             *p = o;
         });
+        tb_retire(c5);
         tb_planes_out<64>(AP, q3.dg1p + (long long)b * (2 * TB_AP_PLANE), t);      // dg1 = df1 planes
     }
     raw_barrier();
@@ -1078,6 +1214,12 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
     const tb_bwd_args q4 = tb_args_again(a0);                 // (see tb_args_again)
     // ---- T4: LayerNorm1': dr1 -> HBM (the residual path into dh), da1 = dropout'(dr1) -> A planes (T5 copies them to HBM)
     {
+        // (the lane index through an opaque copy: T1 walks the same rows and columns, and the LDS offsets and Philox index products the two passes have in
+        //  common, shared by the optimiser, would live from T1 through the GEMM phases between them -- a dozen registers that spill there)
+        int lane4 = lane;
+#if !defined(EEG_EMU)
+        asm volatile("" : "+v"(lane4));
+#endif
         float pe[2][4], po[2][4];
 #pragma unroll
         for (int v = 0; v < 2; ++v)
@@ -1088,19 +1230,19 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
         for (int par = 0; par < 2; ++par)
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-                const int cp = 4 * lane - 2 * par + 2 * p;
+                const int cp = 4 * lane4 - 2 * par + 2 * p;
                 pg1[par][p] = (cp >= 0 && cp < TB_D) ? *reinterpret_cast<const tb_f2*>(q4.ln1_g + cp) : tb_f2{0.f, 0.f};
             }
 #pragma unroll
         for (int rr = 0; rr < 8; ++rr)
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-                const int cp = 4 * lane - ((rr & 1) ? 2 : 0) + 2 * p;
+                const int cp = 4 * lane4 - ((rr & 1) ? 2 : 0) + 2 * p;
                 in_r1[rr][p] = (cp >= 0 && cp < TB_D) ? *reinterpret_cast<const tb_f2*>(q4.r1 + (long long)b * (TB_L * TB_D) + (unsigned)((8 * w + rr) * TB_D + cp)) : tb_f2{0.f, 0.f};
             }
 #pragma unroll
         for (int rr = 0; rr < 8; ++rr) {
-            const int r = 8 * w + rr, c0 = 4 * lane - ((rr & 1) ? 2 : 0);
+            const int r = 8 * w + rr, c0 = 4 * lane4 - ((rr & 1) ? 2 : 0);
             const long long row = (long long)b * TB_L + r, rbase = row * TB_D;
             float dy[4], x1[4], g1[4];
             bool ok[2];
@@ -1129,10 +1271,10 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
                 }
                 if (cp >= 0 && cp < 256) tb_store_planes2(AP, TB_AP_PLANE, ap_off(r, cp), ok[p] ? d0 : 0.f, ok[p] ? d1 : 0.f);
             }
-            if ((rr & 1) && lane == 63) tb_store_planes2(AP, TB_AP_PLANE, ap_off(r, 254), 0.f, 0.f);
+            if ((rr & 1) && lane4 == 63) tb_store_planes2(AP, TB_AP_PLANE, ap_off(r, 254), 0.f, 0.f);
         }
         raw_barrier();                                               // (the scratch rows of T1 have been read by every thread)
-        tb_reduce_partials<2>(SC, w, lane, t, pe, po, part + 4 * 256);
+        tb_reduce_partials<2>(SC, w, lane4, t, pe, po, tb_args_again(a0).partials + (long long)b * (6 * 256) + 4 * 256, none);
     }
     raw_barrier();
 
@@ -1140,7 +1282,7 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_a_kernel(const 
     // ---- T5: dctx = da1 Wo -> HBM, natural (row, 248) layout (the packed operand's columns are 64 head + d)
     {
         f32x4 acc[4][2];
-        tb_gemm<2, 3u, TB_BWD_PF, true, true>(AP, q5.packed + TB_OFF_OT + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc);
+        tb_gemm<2, 3u, 2, true>(AP, q5.packed + TB_OFF_OT + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc, c5, nullptr, none);
         tb_for_tiles(w, lane, 256, acc, [&](int m, int n0, int valid, f32x4& v) {
             const int head = n0 >> 6, d0 = n0 & 63;
             if (d0 < TB_E) tb_st4(q5.dctx + (long long)b * (TB_L * TB_HE) + (unsigned)(m * TB_HE + head * TB_E + d0), TB_E - d0 >= 4 ? 4 : 2, v);
@@ -1158,6 +1300,8 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_b_kernel(const 
     const int b = blockIdx.x;
     const float ksc = (TRAIN && a.drop_p > 0.f) ? 1.f / (1.f - a.drop_p) : 1.f;
     f32x4 acc[4][2];
+    tb_none none;
+    tb_frags<2> ck, cv;                                              // the first k-steps of the dk and the dv GEMM, requested under the GEMM before
     // dq | dk | dv of the sample arrive as token planes = AP images (csrc/attention_x3.hip writes them; columns 64 head + 62, 63 are exact zeros): LDS-DMA
     // copies, no VGPRs and no fp32 -> hi | lo split here.  Wave w deposits rows 8 w .. 8 w + 7 of both planes (1 KB = 2 rows per instruction; the
     // lane picks the source chunk so that the AP swizzle comes out).  dq -> AP and dk -> the XF region at once, dv -> AP when the first GEMM is done.
@@ -1173,15 +1317,16 @@ __global__ __launch_bounds__(TB_THREADS, 2) void token_block_bwd_b_kernel(const 
     dma_planes(1, XF);
     wait_vmcnt<8>();
     raw_barrier();
-    tb_gemm<2, 3u, TB_BWD_PF, true, true>(AP, a.packed + TB_OFF_QT + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc);
+    tb_gemm<2, 3u, 2, true>(AP, a.packed + TB_OFF_QT + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc, none, a.packed + TB_OFF_QT + TB_MAT_ELEMS + (long long)(2 * w) * TB_KS * TB_TILE, ck);
     raw_barrier();                                                   // every wave has read the dq planes
     dma_planes(2, AP);
-    wait_vmcnt<8>();
+#pragma unroll
+    for (int p = 0; p < 2; ++p) tb_wait_frags<2>(8, ck.h[p], ck.l[p]);   // (vmcnt(8): all but the 8 unconditional copies of dv just issued -- the dk planes and ck)
     raw_barrier();
-    tb_gemm<2, 3u, TB_BWD_PF, false, true>(XF, a.packed + TB_OFF_QT + TB_MAT_ELEMS + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc);
-    wait_vmcnt<0>();
+    tb_gemm<2, 3u, 2, false>(XF, a.packed + TB_OFF_QT + TB_MAT_ELEMS + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc, ck, a.packed + TB_OFF_QT + 2 * TB_MAT_ELEMS + (long long)(2 * w) * TB_KS * TB_TILE, cv);
+    tb_retire(cv);                                                   // (vmcnt(0): the dv planes too)
     raw_barrier();
-    tb_gemm<2, 3u, TB_BWD_PF, false, true>(AP, a.packed + TB_OFF_QT + 2 * TB_MAT_ELEMS + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc);
+    tb_gemm<2, 3u, 2, false>(AP, a.packed + TB_OFF_QT + 2 * TB_MAT_ELEMS + (long long)(2 * w) * TB_KS * TB_TILE, lane, acc, cv, nullptr, none);
     raw_barrier();                                                   // (the dk planes in the XF region are dead: the epilogue writes its fp32 image there)
     // + the residual-path gradient, then the embedding dropout' over the flat sample (one Philox block = 4 consecutive flat elements)
     tb_for_tiles(w, lane, TB_D, acc, [&](int m, int n0, int valid, f32x4& v) {
