@@ -16,7 +16,7 @@ tests/test_clip_vision_layout.py pins that restatement to transformers itself:
 Arithmetic (the wrappers of ops16.py; no library GEMM, no torch math op, no eager fallback; bit-reproducible): three launches to hidden_states[0] --
 csrc/clip_vision.hip patch_rows16 (pixels -> GEMM rows, the class slot a zero row, optional per-channel normalisation), ONE csrc/gemm16.hip launch against the
 patch weight packed to (C, Kpad), csrc/clip_vision.hip embed_ln16 (+ position row, row 0 carrying the class embedding, then pre_layrnorm) -- then the layers
-on gemm16 / layernorm16 / act16 and csrc/self_attn.hip (head dim 64) or csrc/attn80.hip (head dim 80).  Resizing and cropping are preprocess.py's; there is
+on gemm16 / layernorm16 / act16 and csrc/self_attn.hip (head dim 64 or 80).  Resizing and cropping are preprocess.py's; there is
 no interpolate_pos_encoding: a pixel tensor of another size raises.
 """
 from types import SimpleNamespace

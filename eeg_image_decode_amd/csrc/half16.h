@@ -1,5 +1,5 @@
 // The 16-bit (fp16 / bf16 I/O) device layer, one definition each, shared by every 16-bit kernel file (gemm16, vae, unet, clip_text, caption, convt16,
-// convt16_bwd, bn2d16, cross_attn, self_attn, vae_attn): the vector types, 16-bit <-> fp32 conversion selected by the template flag F16, the f16 forms
+// convt16_bwd, bn2d16, cross_attn, self_attn at both head dims, vae_attn): the vector types, 16-bit <-> fp32 conversion selected by the template flag F16, the f16 forms
 // of the 16x16x32 and 32x32x16 MFMAs (the bf16 forms are in eeg_common.h) with their selectors, the base-2 exponent of the softmax, and the host-side
 // dtype check.  The transposed LDS read (lds_read_tr16, s16x4) and sched_fence() come with eeg_common.h.
 #pragma once

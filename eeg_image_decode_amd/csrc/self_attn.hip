@@ -1,7 +1,10 @@
-// Flash-style attention for the SDXL UNet's self-attention (attn1; call site Generation/custom_pipeline.py:365-373, the UNet call; the
-// arithmetic is diffusers' AttnProcessor2_0, head_dim 64):
+// Flash-style attention at head dims 64 and 80, one kernel template.
+// 64: the SDXL UNet's self-attention (attn1; call site Generation/custom_pipeline.py:365-373, the UNet call; the arithmetic is diffusers'
+// AttnProcessor2_0), CLIP's text encoders (CAUSAL), GIT's caption decoder (PREFIX-CAUSAL) and GIT's ViT-L/14 image tower.
+// 80: CLIP ViT-H/14's image tower (1280 wide, 16 heads; the IP-Adapter's models/image_encoder, transformers' CLIPVisionModelWithProjection -- the
+// encoder behind the `image_embeds` of Generation/custom_pipeline.py:365-373 and behind the data sets' cached features); no mask.
 //
-//     out[b, i, 64h .. 64h+63] = sum_j softmax_j(scale * q[b,i,h] . k[b,j,h]) v[b,j,h]          i < Tq, j < Tk
+//     out[b, i, D h .. D h + D - 1] = sum_j softmax_j(scale * q[b,i,h] . k[b,j,h]) v[b,j,h]          i < Tq, j < Tk
 //
 // A workgroup (4 waves) owns 64 * QT query rows of one (sample, head); a wave owns QT query tiles of 16 with their Q fragments in registers.
 // K / V stream through LDS in tiles of 64 keys with an online softmax; no score matrix is ever written.
@@ -10,9 +13,21 @@
 //     the sum), and the rounded probabilities are already the B operand of O^T = V^T P^T.
 //   * V stays row-major in LDS (plain 16-byte stores from the staging registers); the V^T operand of P V comes out of ds_read_b64_tr_b16
 //     (two 4-key x 16-column transposed reads per fragment), matching the k-slot permutation of the probabilities (tile pair 2u / 2u+1).
-//   * K and V rows padded to 80 halfs (160 B): the ds_read_b128 K reads and the transposed V reads of a 32-lane half hit distinct banks.
-//   * Register-staged double buffer: the global loads of tile t+1 are issued before tile t is computed and written to the other LDS buffer
-//     after it, one barrier per tile.
+//   * K and V rows of 80 halfs (160 B) at both head dims: the 128-byte rows of head dim 64 are padded to it, at 80 it is the row itself.  160 B = 10
+//     sixteen-byte slots, and 10 r mod 16 visits the even slots once per 8 rows.  A ds_read_b128 lane group is 8 rows of lane group g and the other 8
+//     rows of g + 1 (one slot further: the odd slots), 16 distinct slots = all 64 banks once.  A 32-lane half of a transposed V read is 8 rows x 32
+//     contiguous bytes at bank offsets 40 r mod 64 = {0, 40, 16, 56, 32, 8, 48, 24}: 8 disjoint runs of 8 banks.  Both conflict-free (computed with the
+//     bank rule (address / 4) mod 64 of these two instructions; not measured with a counter).  Two (K, V) buffers of 64 x 160 B: 40 KB per workgroup.
+//   * Register-staged double buffer (flash_stage, csrc/flash16.h): the global loads of tile t+1 are issued before tile t is computed and written to
+//     the other LDS buffer after it, one barrier per tile.  A tile is 64 keys x D / 8 sixteen-byte pieces for 256 threads: 512 at 64, two per thread;
+//     640 at 80, two per thread and a third for threads 0..127, and with 10 pieces per 160-byte row piece i sits at byte 16 i: a linear copy.
+// What 80 changes, all of it compile-time geometry (KS, DN, sa_frag_exists, flash_stage):
+//   * S^T takes KS = 3 k-steps of 32: columns 0..31, 32..63 and 64..95, of which 80..95 (lane groups g = 2, 3 of the third step) do not exist.  Both
+//     operands are ZERO there and neither zero comes from memory: those lanes never load -- not from global memory (past column 80 of a head lies the
+//     next head, k or v of a fused buffer, the next row or the end of the allocation) and not from LDS (where the next key's row starts) -- their Q
+//     and K fragments of the third step are the constant 0 in registers.  0 * 0 adds nothing; a NaN that happened to lie there would.
+//   * O^T has DN = 5 tiles of 16 rows, ten MFMAs per key tile and query tile.
+//   * 64 queries per workgroup only (QT = 1), no causal form: see sa_forward.
 // Numerics: fp32 scores; base-2 softmax, exponent (s - m) * scale * log2(e) on the raw scores (scale > 0).  Not one FMA s * c - m * c: at
 // |scores| ~ 1e9 (inputs near the fp16 range) the rounding of m * c alone is thousands, and the row maximum's exponent would overflow or vanish;
 // s - m is exact near the maximum and never positive.
@@ -27,13 +42,15 @@
 // runtime bound, key j reaches query i iff j < max(i + 1, prefix) -- the image tokens see each other, everything after them is causal.  prefix = 0 is the
 // causal form, bit for bit (the same instructions on the same operands).  A workgroup's key loop ends at max(its last query + 1, prefix) and only the
 // tiles that reach past max(its first query + 1, prefix) are masked.
+// Resources (hipcc -O3 --offload-arch=gfx950, kernel metadata; VGPRs + AGPRs, fp16 and bf16 alike; no spills, no scratch; tests/test_flash_attn_build.py
+// holds the occupancies): D = 64, QT = 2: 164 + 32, 2 waves per SIMD; QT = 1: 108 + 16, causal 112 + 16, 4 waves;
+// D = 80 (QT = 1): 132 + 20, 3 waves.
 #include "flash16.h"
 
 namespace eeg {
 
-constexpr int SA_D = 64;        // head_dim
 constexpr int SA_KT = 64;       // keys per LDS tile
-constexpr int SA_LD = SA_D + 16;  // LDS row stride in halfs (160 B), K and V
+constexpr int SA_LD = 80;       // LDS row stride in halfs (160 B), K and V, both head dims
 constexpr int SA_TILE = SA_KT * SA_LD;  // halfs per K (or V) tile buffer
 
 struct sa_args {
@@ -45,85 +62,78 @@ struct sa_args {
     int prefix;     // CAUSAL only: keys < prefix are visible to every query (0: plain causal)
 };
 
-// 16-byte pieces of one 64 x 64 tile per thread (256 threads): 2 of K, 2 of V
-struct sa_stage {
-    uint4 k[2], v[2];
-};
-
-__device__ __forceinline__ void sa_issue(sa_stage& r, const sa_args& a, const unsigned short* kb, const unsigned short* vb, int key0) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int i = t + 256 * j, row = i >> 3, c8 = (i & 7) * 8, key = key0 + row;
-        r.k[j] = make_uint4(0, 0, 0, 0);
-        r.v[j] = make_uint4(0, 0, 0, 0);
-        if (key < a.Tk) {
-            r.k[j] = *reinterpret_cast<const uint4*>(kb + key * a.ldk + c8);
-            r.v[j] = *reinterpret_cast<const uint4*>(vb + key * a.ldv + c8);
-        }
-    }
+// does lane group g hold columns 32 s + 8g .. + 7 of a head of D?  (all of them but groups 2, 3 of the third k-step at D = 80)
+template <int D>
+__device__ __forceinline__ bool sa_frag_exists(int s, int g) {
+    return 32 * s + 32 <= D || 32 * s + 8 * g < D;
 }
 
-__device__ __forceinline__ void sa_commit(const sa_stage& r, unsigned short* Ks, unsigned short* Vs) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int i = t + 256 * j, row = i >> 3, c8 = (i & 7) * 8;
-        *reinterpret_cast<uint4*>(Ks + row * SA_LD + c8) = r.k[j];
-        *reinterpret_cast<uint4*>(Vs + row * SA_LD + c8) = r.v[j];
-    }
-}
-
-template <bool F16, int QT, bool CAUSAL = false>
+template <bool F16, int QT, bool CAUSAL, int D>
 __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
+    static_assert(D == 64 || D == 80, "head dim");
+    constexpr int KS = (D + 31) / 32, DN = D / 16;      // k-steps of S^T (the last one partial at 80), 16-row tiles of O^T
     EEG_LDS_BASE(unsigned short, lds);      // [2][K tile | V tile]
     const int b = blockIdx.z, h = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int fr = lane & 15, g = lane >> 4;
-    const unsigned short* kb = a.k + (long long)b * a.Tk * a.ldk + h * SA_D;
-    const unsigned short* vb = a.v + (long long)b * a.Tk * a.ldv + h * SA_D;
+    const unsigned short* kb = a.k + (long long)b * a.Tk * a.ldk + h * D;
+    const unsigned short* vb = a.v + (long long)b * a.Tk * a.ldv + h * D;
     int nkt = (a.Tk + SA_KT - 1) / SA_KT;
     if (CAUSAL) {                                                          // stop after the tile of the workgroup's last query (Tq == Tk)
         const int qend = (int)(blockIdx.x + 1) * (64 * QT), qlast = (qend < a.Tq ? qend : a.Tq) - 1;
         const int klast = qlast + 1 > a.prefix ? qlast : a.prefix - 1;         // the last key any query of the workgroup sees
         if (klast / SA_KT + 1 < nkt) nkt = klast / SA_KT + 1;
     }
+    const bf16x8 zero8 = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
 
-    sa_stage st;
-    sa_issue(st, a, kb, vb, 0);
-    // Q as the B operand of S^T = K Q^T: lane (query fr, group g) holds Q[q][32 s + 8g .. +7]; query tile p of this wave = (p * 4 + wave)
-    bf16x8 bq[QT][2];
+    flash_stage<256, SA_KT, D, SA_LD> st;
+    st.issue(kb, a.ldk, vb, a.ldv, 0, a.Tk);
+    // Q as the B operand of S^T = K Q^T: lane (query fr, group g) holds Q[q][32 s + 8g .. +7], zeros where those columns do not exist; query tile p
+    // of this wave = (p * 4 + wave)
+    bf16x8 bq[QT][KS];
 #pragma unroll
     for (int p = 0; p < QT; ++p) {
         const int qrow = blockIdx.x * (64 * QT) + (p * 4 + wave) * 16 + fr;
-        const unsigned short* qp = a.q + ((long long)b * a.Tq + (qrow < a.Tq ? qrow : a.Tq - 1)) * a.ldq + h * SA_D + 8 * g;
-        bq[p][0] = *reinterpret_cast<const bf16x8*>(qp);
-        bq[p][1] = *reinterpret_cast<const bf16x8*>(qp + 32);
+        const unsigned short* qp = a.q + ((long long)b * a.Tq + (qrow < a.Tq ? qrow : a.Tq - 1)) * a.ldq + h * D + 8 * g;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            bq[p][s] = zero8;
+            if (sa_frag_exists<D>(s, g)) bq[p][s] = *reinterpret_cast<const bf16x8*>(qp + 32 * s);
+        }
     }
-    f32x4 acc[QT][4];
+    f32x4 acc[QT][DN];
     float m[QT], l[QT];
 #pragma unroll
     for (int p = 0; p < QT; ++p) {
         m[p] = -INFINITY;
         l[p] = 0.f;
 #pragma unroll
-        for (int dn = 0; dn < 4; ++dn) acc[p][dn] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int dn = 0; dn < DN; ++dn) acc[p][dn] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    sa_commit(st, lds, lds + SA_TILE);
+    st.commit(lds, lds + SA_TILE);
     __syncthreads();
 
     for (int kt = 0; kt < nkt; ++kt) {
         const unsigned short* Ks = lds + (kt & 1) * 2 * SA_TILE;
         const unsigned short* Vs = Ks + SA_TILE;
-        if (kt + 1 < nkt) sa_issue(st, a, kb, vb, (kt + 1) * SA_KT);      // in flight while this tile is computed
-        // scores of the 4 key tiles of 16
+        if (kt + 1 < nkt) st.issue(kb, a.ldk, vb, a.ldv, (kt + 1) * SA_KT, a.Tk);   // in flight while this tile is computed
+        // scores of the 4 key tiles of 16: the k-steps in order into one accumulator
         f32x4 s[QT][4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const bf16x8 k0 = *reinterpret_cast<const bf16x8*>(Ks + (16 * t + fr) * SA_LD + 8 * g);
-            const bf16x8 k1 = *reinterpret_cast<const bf16x8*>(Ks + (16 * t + fr) * SA_LD + 32 + 8 * g);
+            const unsigned short* kr = Ks + (16 * t + fr) * SA_LD + 8 * g;
+            bf16x8 kf[KS];
 #pragma unroll
-            for (int p = 0; p < QT; ++p) s[p][t] = mma<F16>(k1, bq[p][1], mma<F16>(k0, bq[p][0], f32x4{0.f, 0.f, 0.f, 0.f}));
+            for (int ks = 0; ks < KS; ++ks) {
+                kf[ks] = zero8;
+                if (sa_frag_exists<D>(ks, g)) kf[ks] = *reinterpret_cast<const bf16x8*>(kr + 32 * ks);   // (columns 80 .. 95 would be the next key's row)
+            }
+#pragma unroll
+            for (int p = 0; p < QT; ++p) {
+                s[p][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) s[p][t] = mma<F16>(kf[ks], bq[p][ks], s[p][t]);
+            }
         }
         if ((kt + 1) * SA_KT > a.Tk) {                                     // the last tile, partial: keys >= Tk (zero rows in LDS) -> -inf
 #pragma unroll
@@ -168,16 +178,17 @@ __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
                 }
             l[p] = fmaf(l[p], alpha, sum);                                 // this lane's keys only: reduced across the 4 groups at the end
 #pragma unroll
-            for (int dn = 0; dn < 4; ++dn) acc[p][dn] *= alpha;
+            for (int dn = 0; dn < DN; ++dn) acc[p][dn] *= alpha;
 #pragma unroll
             for (int u = 0; u < 2; ++u) pa[p][u] = flash_pack_p<F16>(s[p][2 * u], s[p][2 * u + 1]);
         }
         // P V: k-step u covers key tiles 2u, 2u+1; lane (query fr, group g) supplies keys {32u+4g+r} U {32u+16+4g+r}; the V^T fragment
         // (d = 16dn + fr, the same keys) is two transposed reads of rows 32u+4g.. / 32u+16+4g.., lane 4q+p addressing row q, columns 4p..
+        // (at most column 16 (DN - 1) + 12 + 3 = D - 1)
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int dn = 0; dn < 4; ++dn) {
+            for (int dn = 0; dn < DN; ++dn) {
                 const unsigned short* vp = Vs + (32 * u + 4 * g + (fr >> 2)) * SA_LD + 16 * dn + 4 * (fr & 3);
                 const s16x4 lo = lds_read_tr16(vp), hi = lds_read_tr16(vp + 16 * SA_LD);
                 const bf16x8 bv = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -186,7 +197,7 @@ __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
             }
         if (kt + 1 < nkt) {
             unsigned short* Kn = lds + ((kt + 1) & 1) * 2 * SA_TILE;        // last read in tile kt-1, before the previous barrier
-            sa_commit(st, Kn, Kn + SA_TILE);
+            st.commit(Kn, Kn + SA_TILE);
         }
         __syncthreads();
     }
@@ -195,10 +206,57 @@ __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
         const float inv = flash_row_inv(l[p]);
         const int qrow = blockIdx.x * (64 * QT) + (p * 4 + wave) * 16 + fr;
         if (qrow < a.Tq) {
-            unsigned short* op = a.out + ((long long)b * a.Tq + qrow) * a.ldo + h * SA_D + 4 * g;
+            unsigned short* op = a.out + ((long long)b * a.Tq + qrow) * a.ldo + h * D + 4 * g;
 #pragma unroll
-            for (int dn = 0; dn < 4; ++dn) flash_store4<F16>(op + 16 * dn, acc[p][dn], inv);
+            for (int dn = 0; dn < DN; ++dn) flash_store4<F16>(op + 16 * dn, acc[p][dn], inv);   // columns 16dn + 4g .. + 3 <= D - 1
         }
+    }
+}
+
+// 64 * QT queries per workgroup
+template <int QT, bool CAUSAL, int D>
+static int sa_launch(const sa_args& a, int B, int heads, bool f16, void* stream) {
+    const size_t lds = sizeof(unsigned short) * 4 * SA_TILE;                // 40 KB: two (K, V) tile buffers
+    const dim3 grid((a.Tq + 64 * QT - 1) / (64 * QT), heads, B);
+    if (f16) EEG_LAUNCH((self_attn_kernel<true, QT, CAUSAL, D>), grid, dim3(256), lds, stream, a);
+    else     EEG_LAUNCH((self_attn_kernel<false, QT, CAUSAL, D>), grid, dim3(256), lds, stream, a);
+    return (int)hipGetLastError();
+}
+
+template <int D>
+static int sa_strides_ok(long long ldq, long long ldk, long long ldv, long long ldo) {
+    if (ldq < D || ldk < D || ldv < D || ldo < D) return EEGCLIP_EINVAL;
+    if ((ldq | ldk | ldv | ldo) & 7) return EEGCLIP_EALIGN;
+    return 0;
+}
+
+template <int D>
+static int sa_forward(bool causal, int prefix, const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B, int Tq,
+                      int Tk, int heads, float scale, int dtype, void* stream) {
+    int rc = sa_strides_ok<D>(ldq, ldk, ldv, ldo);
+    if (rc) return rc;
+    if (heads < 1 || heads > 65535 || (causal && (Tq != Tk || prefix < 0 || prefix > Tk))) return EEGCLIP_EINVAL;
+    const long long C = (long long)heads * D;
+    if (ldq < C || ldk < C || ldv < C || ldo < C) return EEGCLIP_EINVAL;
+    rc = flash_args_ok(q, k, v, out, B, Tq, Tk, scale, dtype);            // (0 = fine)
+    if (rc) return rc;
+    const sa_args a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (unsigned short*)out, ldq, ldk, ldv, ldo, Tq, Tk,
+                    scale * 1.44269504088896340736f, prefix};
+    const bool f16 = dtype == EEGCLIP_DT_F16;
+    if constexpr (D == 80) {
+        // 64 queries per workgroup at every size -- not the 64-wide rule below.  Measured on the MI355X (profiles/clip_vision_bench.json, `query_block_ab`: a build with two query tiles per wave at head dim 80, not in the tree) at the
+        // towers' T = 257, 16 heads, fp16 (bf16 within 2 % of it), microseconds with 64 | 128 queries per workgroup, median of 7 windows whose spread was under
+        // 1 %:  B = 1: 8.8 | 12.2   B = 4: 13.1 | 14.1   B = 8: 20.3 | 19.7   B = 16: 33.5 | 33.5   B = 64: 101.8 | 100.8   B = 256: 388.9 | 420.9.
+        // 128 never wins by more than 3 % and loses 38 % at one image and 8 % at 256: 257 queries are 5 blocks of 64 (320 rows, 80 % used) but 3 of 128 (384 rows,
+        // 67 % used), which at this length costs what the halved K / V traffic saves, and the 128 form ran at 190 + 40 registers (2 waves per SIMD) against 3 waves.
+        // A T of thousands, where the tail no longer matters, was not measured: no caller has one.  Nor has a causal or prefix form a caller: none is built.
+        return sa_launch<1, false, D>(a, B, heads, f16, stream);
+    } else {
+        // 128 queries per workgroup, or 64 when that leaves fewer than two workgroups per CU (256 CUs): SDXL's 1024-token stage at one image is
+        // 160 workgroups of 128
+        const bool wide = (long long)B * heads * ((Tq + 127) / 128) >= 512;
+        if (wide) return causal ? sa_launch<2, true, D>(a, B, heads, f16, stream) : sa_launch<2, false, D>(a, B, heads, f16, stream);
+        return causal ? sa_launch<1, true, D>(a, B, heads, f16, stream) : sa_launch<1, false, D>(a, B, heads, f16, stream);
     }
 }
 
@@ -207,61 +265,34 @@ __global__ __launch_bounds__(256) void self_attn_kernel(const sa_args a) {
 using namespace eeg;
 
 extern "C" int eegclip_self_attn_supported(int head_dim, long long ldq, long long ldk, long long ldv, long long ldo) {
-    if (head_dim != SA_D) return EEGCLIP_EINVAL;
-    if (ldq < SA_D || ldk < SA_D || ldv < SA_D || ldo < SA_D) return EEGCLIP_EINVAL;
-    if ((ldq | ldk | ldv | ldo) & 7) return EEGCLIP_EALIGN;
-    return 0;
-}
-
-static int sa_forward(bool causal, int prefix, const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B, int Tq,
-                      int Tk, int heads, int head_dim, float scale, int dtype, void* stream) {
-    int rc = eegclip_self_attn_supported(head_dim, ldq, ldk, ldv, ldo);
-    if (rc) return rc;
-    if (heads < 1 || heads > 65535 || (causal && (Tq != Tk || prefix < 0 || prefix > Tk))) return EEGCLIP_EINVAL;
-    const long long C = (long long)heads * SA_D;
-    if (ldq < C || ldk < C || ldv < C || ldo < C) return EEGCLIP_EINVAL;
-    rc = flash_args_ok(q, k, v, out, B, Tq, Tk, scale, dtype);            // (0 = fine)
-    if (rc) return rc;
-    const sa_args a{(const unsigned short*)q, (const unsigned short*)k, (const unsigned short*)v, (unsigned short*)out, ldq, ldk, ldv, ldo, Tq, Tk,
-                    scale * 1.44269504088896340736f, prefix};
-    const size_t lds = sizeof(unsigned short) * 4 * SA_TILE;                // 40 KB: two (K, V) tile buffers
-    // 128 queries per workgroup, or 64 when that leaves fewer than two workgroups per CU (256 CUs): SDXL's 1024-token stage at one image is
-    // 160 workgroups of 128
-    const long long wg128 = (long long)B * heads * ((Tq + 127) / 128);
-    const bool f16 = dtype == EEGCLIP_DT_F16;
-    if (wg128 >= 512) {
-        const dim3 grid((Tq + 127) / 128, heads, B);
-        if (causal) {
-            if (f16) EEG_LAUNCH((self_attn_kernel<true, 2, true>), grid, dim3(256), lds, stream, a);
-            else     EEG_LAUNCH((self_attn_kernel<false, 2, true>), grid, dim3(256), lds, stream, a);
-        } else {
-            if (f16) EEG_LAUNCH((self_attn_kernel<true, 2>), grid, dim3(256), lds, stream, a);
-            else     EEG_LAUNCH((self_attn_kernel<false, 2>), grid, dim3(256), lds, stream, a);
-        }
-    } else {
-        const dim3 grid((Tq + 63) / 64, heads, B);
-        if (causal) {
-            if (f16) EEG_LAUNCH((self_attn_kernel<true, 1, true>), grid, dim3(256), lds, stream, a);
-            else     EEG_LAUNCH((self_attn_kernel<false, 1, true>), grid, dim3(256), lds, stream, a);
-        } else {
-            if (f16) EEG_LAUNCH((self_attn_kernel<true, 1>), grid, dim3(256), lds, stream, a);
-            else     EEG_LAUNCH((self_attn_kernel<false, 1>), grid, dim3(256), lds, stream, a);
-        }
-    }
-    return (int)hipGetLastError();
+    if (head_dim != 64) return EEGCLIP_EINVAL;
+    return sa_strides_ok<64>(ldq, ldk, ldv, ldo);
 }
 
 extern "C" int eegclip_self_attn_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo,
                                      int B, int Tq, int Tk, int heads, int head_dim, float scale, int dtype, void* stream) {
-    return sa_forward(false, 0, q, ldq, k, ldk, v, ldv, out, ldo, B, Tq, Tk, heads, head_dim, scale, dtype, stream);
+    if (head_dim != 64) return EEGCLIP_EINVAL;
+    return sa_forward<64>(false, 0, q, ldq, k, ldk, v, ldv, out, ldo, B, Tq, Tk, heads, scale, dtype, stream);
 }
 
 extern "C" int eegclip_self_attn_causal_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo,
                                             int B, int Tq, int Tk, int heads, int head_dim, float scale, int dtype, void* stream) {
-    return sa_forward(true, 0, q, ldq, k, ldk, v, ldv, out, ldo, B, Tq, Tk, heads, head_dim, scale, dtype, stream);
+    if (head_dim != 64) return EEGCLIP_EINVAL;
+    return sa_forward<64>(true, 0, q, ldq, k, ldk, v, ldv, out, ldo, B, Tq, Tk, heads, scale, dtype, stream);
 }
 
 extern "C" int eegclip_self_attn_prefix_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo,
                                             int B, int T, int prefix, int heads, int head_dim, float scale, int dtype, void* stream) {
-    return sa_forward(true, prefix, q, ldq, k, ldk, v, ldv, out, ldo, B, T, T, heads, head_dim, scale, dtype, stream);
+    if (head_dim != 64) return EEGCLIP_EINVAL;
+    return sa_forward<64>(true, prefix, q, ldq, k, ldk, v, ldv, out, ldo, B, T, T, heads, scale, dtype, stream);
+}
+
+// head dim 80: eegclip_self_attn_fwd's contract with C = 80 * heads, no head_dim argument
+extern "C" int eegclip_attn80_supported(long long ldq, long long ldk, long long ldv, long long ldo) {
+    return sa_strides_ok<80>(ldq, ldk, ldv, ldo);
+}
+
+extern "C" int eegclip_attn80_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B, int Tq,
+                                  int Tk, int heads, float scale, int dtype, void* stream) {
+    return sa_forward<80>(false, 0, q, ldq, k, ldk, v, ldv, out, ldo, B, Tq, Tk, heads, scale, dtype, stream);
 }

@@ -4,7 +4,7 @@
 //     out[b, i, :] = sum_j softmax_j(scale * q[b,i] . k[b,j]) v[b,j]          i, j < T,  head_dim D = 128 NC, NC = 1 .. 4
 //
 // csrc/self_attn.hip with a wide head: the same transposed scores, online softmax, row-major V read through ds_read_b64_tr_b16 and register-staged
-// double buffer; what changes is the budget.  16 queries x 512 columns of fp32 O are 128 registers per lane, which with the Q fragments (64) and the
+// double buffer (flash_stage, csrc/flash16.h); what changes is the budget.  16 queries x 512 columns of fp32 O are 128 registers per lane, which with the Q fragments (64) and the
 // staging registers of a K / V tile leaves one wave per SIMD, the accumulators in the AGPR half of the file and every rescale of O a round trip
 // through the vector registers.  So the head is SPLIT IN TWO across waves: a workgroup of 8 waves (two per SIMD, 256 registers each, all of them
 // plain VGPRs) owns 64 query rows of one image; wave (query tile qt = wave & 3, half h = wave >> 2) holds columns [h D/2, (h+1) D/2) of its 16
@@ -42,39 +42,6 @@ struct va_args {
     float scale2;   // scale * log2(e)
 };
 
-// 16-byte pieces of one 32 x D tile per thread (512 threads): NC of K, NC of V; piece i = row i / (D / 8), columns 8 (i % (D / 8))
-template <int NC>
-struct va_stage {
-    uint4 k[NC], v[NC];
-};
-
-template <int NC>
-__device__ __forceinline__ void va_issue(va_stage<NC>& r, const va_args& a, const unsigned short* kb, const unsigned short* vb, int key0) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        const int i = t + 512 * j, row = i / (16 * NC), c8 = (i % (16 * NC)) * 8, key = key0 + row;
-        r.k[j] = make_uint4(0, 0, 0, 0);
-        r.v[j] = make_uint4(0, 0, 0, 0);
-        if (key < a.T) {
-            r.k[j] = *reinterpret_cast<const uint4*>(kb + key * a.ldk + c8);
-            r.v[j] = *reinterpret_cast<const uint4*>(vb + key * a.ldv + c8);
-        }
-    }
-}
-
-template <int NC>
-__device__ __forceinline__ void va_commit(const va_stage<NC>& r, unsigned short* Ks, unsigned short* Vs) {
-    constexpr int LD = 128 * NC + VA_PAD;
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-        const int i = t + 512 * j, row = i / (16 * NC), c8 = (i % (16 * NC)) * 8;
-        *reinterpret_cast<uint4*>(Ks + row * LD + c8) = r.k[j];
-        *reinterpret_cast<uint4*>(Vs + row * LD + c8) = r.v[j];
-    }
-}
-
 template <bool F16, int NC>
 __global__ __launch_bounds__(512) void vae_attn_kernel(const va_args a) {
     constexpr int D = 128 * NC, DH = D / 2, LD = D + VA_PAD, TILE = VA_KT * LD;      // TILE: halfs per K (or V) tile buffer
@@ -88,8 +55,8 @@ __global__ __launch_bounds__(512) void vae_attn_kernel(const va_args a) {
     const unsigned short* vb = a.v + (long long)b * a.T * a.ldv;
     const int nkt = (a.T - 1) / VA_KT + 1;
 
-    va_stage<NC> st;
-    va_issue<NC>(st, a, kb, vb, 0);
+    flash_stage<512, VA_KT, D, LD> st;       // NC pieces of K and of V per thread
+    st.issue(kb, a.ldk, vb, a.ldv, 0, a.T);
     // Q as the B operand of S^T = K Q^T: lane (query fr, group g) holds Q[q][DH h + 32 s + 8g .. +7], s < 2 NC
     const int qrow = blockIdx.x * 64 + qt * 16 + fr;
     bf16x8 bq[2 * NC];
@@ -102,13 +69,13 @@ __global__ __launch_bounds__(512) void vae_attn_kernel(const va_args a) {
 #pragma unroll
     for (int dn = 0; dn < DN; ++dn) acc[dn] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = -INFINITY, l = 0.f;
-    va_commit<NC>(st, lds, lds + TILE);
+    st.commit(lds, lds + TILE);
     __syncthreads();
 
     for (int kt = 0; kt < nkt; ++kt) {
         const unsigned short* Ks = lds + (kt & 1) * 2 * TILE;
         const unsigned short* Vs = Ks + TILE;
-        if (kt + 1 < nkt) va_issue<NC>(st, a, kb, vb, (kt + 1) * VA_KT);   // in flight while this tile is computed
+        if (kt + 1 < nkt) st.issue(kb, a.ldk, vb, a.ldv, (kt + 1) * VA_KT, a.T);   // in flight while this tile is computed
         // this wave's half of the scores of the 2 key tiles of 16: fragment i of group p is (tile t = i & 1, k-step 2p + (i >> 1)), so that
         // consecutive MFMAs go round the four accumulators sc[t][step & 1]; the reads of group p + 1 are issued ahead of the MFMAs of group p
         f32x4 sc[2][2];
@@ -189,7 +156,7 @@ __global__ __launch_bounds__(512) void vae_attn_kernel(const va_args a) {
         }
         if (kt + 1 < nkt) {
             unsigned short* Kn = lds + ((kt + 1) & 1) * 2 * TILE;           // last read in tile kt-1, before the previous barrier
-            va_commit<NC>(st, Kn, Kn + TILE);
+            st.commit(Kn, Kn + TILE);
         }
         __syncthreads();                                                   // (also: the exchange is read before it is written again)
     }

@@ -1,7 +1,7 @@
 """The 16-bit host layer of the generation stack: what sdxl.py (processors, stand-in UNet), sdxl_unet.py, clip_text.py and vae.py share.
 
 * thin wrappers over the 16-bit entry points, free functions taking tensors: linear16 / linear (csrc/gemm16.hip, csrc/vae.hip conv16 as a 1 x 1
-  convolution), linear16_skinny / decode_attention (csrc/caption.hip), self_attention (csrc/self_attn.hip, csrc/attn80.hip), vae_attention (csrc/vae_attn.hip), cross_attention (csrc/cross_attn.hip), layernorm16 / geglu16 / concat16 (csrc/unet.hip),
+  convolution), linear16_skinny / decode_attention (csrc/caption.hip), self_attention (csrc/self_attn.hip, head dims 64 and 80), vae_attention (csrc/vae_attn.hip), cross_attention (csrc/cross_attn.hip), layernorm16 / geglu16 / concat16 (csrc/unet.hip),
   act16 / gather_rows16 (csrc/clip_text.hip), patch_rows16 / embed_ln16 (csrc/clip_vision.hip), conv_transpose16 (csrc/convt16.hip).  No library GEMM, no eager fallback: a shape a kernel does not take raises.
 * PackedWeights: the one cache of repacked weights and the one statement of its key.
 * seeded_parameters: the construction of a module whose nn children hold parameters only and are never called.
@@ -134,7 +134,7 @@ def _flash_operands(name, q, k, v, out, check_shapes):
 
 
 def self_attention(q, k, v, heads, scale=None, out=None, causal=False, prefix=None, head_dim=64):
-    """softmax(scale * q k^T) v per head of `head_dim` (flash-style: no T x T buffer): 64 on csrc/self_attn.hip, 80 on csrc/attn80.hip (CLIP ViT-H/14; no
+    """softmax(scale * q k^T) v per head of `head_dim` (flash-style: no T x T buffer): 64 or 80, both csrc/self_attn.hip (80: eegclip_attn80_fwd, CLIP ViT-H/14; no
     mask: causal / prefix raise).  q (B, Tq, C), k / v (B, Tk, C), C = heads * head_dim,
     fp16 or bf16; the three may be column slices of one fused (B, T, 3C) projection (consumed in place).  scale defaults to head_dim ** -0.5 (diffusers'
     attn.scale: 1/8 at 64).  causal: key j reaches query i only if j <= i (CLIP's text encoders; Tq == Tk).  prefix (an int in [0, T]; Tq == Tk): key j reaches
@@ -146,7 +146,7 @@ def self_attention(q, k, v, heads, scale=None, out=None, causal=False, prefix=No
     if head_dim not in (64, 80):
         raise EegclipError(f"self_attention: head_dim must be 64 or 80 (got {head_dim})")
     if head_dim == 80 and causal:
-        raise EegclipError("self_attention: head_dim 80 (csrc/attn80.hip) has no causal / prefix form")
+        raise EegclipError("self_attention: head_dim 80 has no causal / prefix form")
     def check_shapes():
         if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
             raise EegclipError("self_attention takes (B, T, C) tensors")

@@ -454,7 +454,7 @@ int eegclip_self_attn_causal_fwd(const void* q, long long ldq, const void* k, lo
 int eegclip_self_attn_prefix_fwd(const void* q, long long ldq, const void* k, long long ldk, const void* v, long long ldv, void* out, long long ldo, int B,
                                  int T, int prefix, int heads, int head_dim, float scale, int dtype, void* stream);
 
-/* ---- attention at head dim 80 (csrc/attn80.hip; CLIP ViT-H/14's image tower = the IP-Adapter's models/image_encoder, transformers'
+/* ---- attention at head dim 80 (csrc/self_attn.hip's template at head dim 80; CLIP ViT-H/14's image tower = the IP-Adapter's models/image_encoder, transformers'
  * CLIPVisionModelWithProjection: the encoder of the `image_embeds` that Generation/custom_pipeline.py:365-373 conditions on).  (ABI 19.)
  *   out[b, i, 80h .. 80h+79] = sum_j softmax_j(scale * q[b,i,h] . k[b,j,h]) v[b,j,h]          i < Tq, j < Tk, h < heads          (no mask)
  * eegclip_self_attn_fwd's contract with C = 80 * heads: rows addressed through ldq / ldk / ldv / ldo (elements), a fused (B*T, 3C) projection consumed in

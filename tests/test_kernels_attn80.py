@@ -1,4 +1,4 @@
-"""csrc/attn80.hip: flash-style attention at head dim 80 (CLIP ViT-H/14's image tower), 16-bit I/O, against an fp64 softmax(scale q k^T) v on the 16-bit-rounded
+"""csrc/self_attn.hip at head dim 80 (eegclip_attn80_fwd): flash-style attention (CLIP ViT-H/14's image tower), 16-bit I/O, against an fp64 softmax(scale q k^T) v on the 16-bit-rounded
 inputs, on the lane emulator and on the GPU.  Tolerances are tests/test_kernels_self_attn.py's: the arithmetic is the same (16-bit probabilities and output,
 fp32 accumulation) and with scale = 80^-1/2 on standard normal inputs the scores have the same unit variance."""
 import numpy as np

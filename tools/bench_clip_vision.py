@@ -1,8 +1,8 @@
-"""CLIP's vision towers (eeg_image_decode_amd/clip_vision.py) and the head-dim-80 attention kernel (csrc/attn80.hip) on the GPU.  Prints one JSON object.
+"""CLIP's vision towers (eeg_image_decode_amd/clip_vision.py) and the attention kernel at head dim 80 (csrc/self_attn.hip's template) on the GPU.  Prints one JSON object.
 
-  attention  csrc/attn80.hip at (B, T, heads) = (1 | 16 | 256, 257, 16), fp16 and bf16, on a fused (B, T, 3C) buffer: microseconds and the fraction of the
+  attention  csrc/self_attn.hip at head dim 80 (eegclip_attn80_fwd; `attn80` in the rows) at (B, T, heads) = (1 | 16 | 256, 257, 16), fp16 and bf16, on a fused (B, T, 3C) buffer: microseconds and the fraction of the
              2.5 PF/s dense 16-bit peak in USEFUL FLOPs (4 B heads T T 80: the zero half of the third k-step is not counted); beside each the 64-wide
-             csrc/self_attn.hip at the same B, T, heads (4 B heads T T 64) and torch's scaled_dot_product_attention at head dim 80 on the same tensors.
+             instantiation at the same B, T, heads (4 B heads T T 64) and torch's scaled_dot_product_attention at head dim 80 on the same tensors.
              `cost_per_useful_flop_vs_64` = (attn80 us / its FLOPs) / (64-wide us / its FLOPs): 96 / 80 = 1.2 is what the padded third k-step alone costs.
   towers     ip_adapter_image_encoder() and git_vision_tower(), fp16, ms per image at B = 1, 16, 64; beside it transformers' own model with the same
              weights in fp16 on the same GPU; the C-ABI calls of one forward, counted (each is one kernel launch: 3 to hidden_states[0], 8 per layer,
@@ -17,7 +17,7 @@ spread.  The three attention kernels alternate inside a round of windows, so tha
 
 --out FILE updates FILE: the keys this run computes are replaced, every other key of an existing FILE stays (`kernel_families` from a --kernel-stats run,
 `model_errors` = the figures tests/test_clip_vision_gpu.py prints, `query_block_ab` = the 64 | 128 queries per workgroup comparison taken with a second
-build of csrc/attn80.hip that is not in the tree); each of those sections says where it came from.
+build at head dim 80, two query tiles per wave, that is not in the tree); each of those sections says where it came from.
 """
 import argparse
 import json
@@ -32,8 +32,9 @@ from bench_clip_text import kernel_split  # noqa: E402  (the rocprofv3 kernel_st
 
 PEAK = 2.5e15
 T, HEADS = 257, 16
-FAMILIES = (("gemm", ("gemm16",)), ("attention", ("attn80_kernel", "self_attn_kernel")), ("layernorm", ("layernorm16", "embed_ln16")),
+FAMILIES = (("gemm", ("gemm16",)), ("attention", ("self_attn_kernel",)), ("layernorm", ("layernorm16", "embed_ln16")),
             ("activation", ("act16",)), ("patch rows", ("patch_rows16",)))
+# attention: both towers run instantiations of one template (head dim 80 and 64), whose names begin alike; the traced pass runs nothing else that matches
 SETUP = "setup (torch: weight init, fp16 cast, q|k|v and patch-weight packing, random pixels)"
 
 

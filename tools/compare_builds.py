@@ -16,6 +16,9 @@ Cases (the child uses public names only, so it runs under both trees):
                    the logits and the ids; ms = median of 5 further forward + generate runs, host clock
   low_level        a reduced-width LowLevelEncoder (hidden 128, widths 256-128-64-64-4, bf16, B = 16): forward, then one LowLevelTrainer.step -- sha256 over
                    the latent and every parameter gradient (the loss is an atomic sum); ms = median of 5 further steps, host clock
+  clip_vision      two reduced CLIPVisionEncoders (2 layers, fp16) on 2 seeded 224 x 224 images (257 tokens): hidden 640 = 8 heads of 80 with a projection
+                   and hidden 512 = 8 heads of 64 without one (post_layernorm on every token) -- sha256 over image_embeds / last_hidden_state and
+                   the hidden states; ms = median of 5 further forwards of both, host clock
 
 Time: the other tree's own runs are the reference.  This tree's median per case must lie within the other tree's [min, max] widened on both sides by
 its spread (max - min); `within_range` records it.  Exit status 1 if a digest differs or a case is outside its range."""
@@ -28,7 +31,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ("weights", "vae_decode", "unet_512_b1", "unet_1024_b2", "text_encoder", "text_encoder_2", "standin_loop", "standin_loop_sa", "git_caption",
-         "low_level")
+         "low_level", "clip_vision")
 
 CHILD = r"""
 import hashlib, json, statistics, sys, time
@@ -155,9 +158,21 @@ def low_level():
     return {"sha256": digest, "ms": host_ms(lambda: trainer.step(x, target), 5)}
 
 
+def clip_vision():
+    from eeg_image_decode_amd.clip_vision import CLIPVisionEncoder
+    towers = (CLIPVisionEncoder(640, 1280, 2, 8, "gelu", 128, dtype=torch.float16, device="cuda", seed=2),
+              CLIPVisionEncoder(512, 1024, 2, 8, "quick_gelu", None, post_layernorm_all=True, dtype=torch.float16, device="cuda", seed=2))
+    px = torch.randn(2, 3, 224, 224, generator=torch.Generator().manual_seed(8)).to("cuda", torch.float16)
+    run = lambda: [m(px, output_hidden_states=True) for m in towers]
+    h80, h64 = run()
+    digest = sha(h80.image_embeds, h80.last_hidden_state, *h80.hidden_states, h64.last_hidden_state, *h64.hidden_states)
+    return {"sha256": digest, "ms": host_ms(run, 5)}
+
+
 table = {"weights": weights, "vae_decode": vae_decode, "unet_512_b1": lambda: unet(1, 64), "unet_1024_b2": lambda: unet(2, 128),
          "text_encoder": lambda: text_encoder(0), "text_encoder_2": lambda: text_encoder(1), "standin_loop": lambda: standin_loop(False),
-         "standin_loop_sa": lambda: standin_loop(True), "git_caption": git_caption, "low_level": low_level}
+         "standin_loop_sa": lambda: standin_loop(True), "git_caption": git_caption, "low_level": low_level,
+         "clip_vision": clip_vision}
 res = {}
 for c in cases:
     if not c.startswith("unet"):
