@@ -153,9 +153,10 @@ class PlanOp(C.Structure):
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_GRAD = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3 = 0, 1
-ABI_VERSION = 20
+ABI_VERSION = 21
 DT_BF16, DT_F16, DT_F32 = 0, 1, 2
 SRC_U8_HWC, RESIZE_BILINEAR, RESIZE_BICUBIC = 3, 2, 3
+SSIM_TILE_H, SSIM_TILE_W = 32, 32
 _P, _I, _F, _L, _U64, _U, _D = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_ulonglong, C.c_uint, C.c_double
 
 # name -> argtypes   (restype is always int)
@@ -318,6 +319,10 @@ PROTOTYPES = {
     "eegclip_cstack_bwd_taps_reduce": [_P, _I, _P, _P],
     "eegclip_cstack_bwd_w2_workspace_floats": [_I, _I],
     "eegclip_cstack_bwd_w2": [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "eegclip_pixcorr_ssim_workspace_bytes": [_I, _I, _I],
+    "eegclip_pixcorr_ssim": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    "eegclip_two_way_workspace_bytes": [_I, _I],
+    "eegclip_two_way": [_P, _P, _I, _I, _P, _P, _P, _L, _P],
     "eegclip_plan_fn_id": [C.c_char_p],
     "eegclip_plan_events": [_I, C.POINTER(C.c_void_p)],
     "eegclip_plan_events_destroy": [_I, C.POINTER(C.c_void_p)],

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 20
+#define EEGCLIP_ABI_VERSION 21
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -1093,6 +1093,31 @@ int eegclip_cstack_bwd_taps_reduce(const float* dw_partials, int B, float* dw25,
 long long eegclip_cstack_bwd_w2_workspace_floats(int B, int H);
 int eegclip_cstack_bwd_w2(const float* x, long long xs_b, long long xs_h, const float* w25, const float* bias1, const float* mean1, const float* rstd1,
                           const float* gamma1, const float* beta1, const float* dy2, float* dWs, float* workspace, int B, int H, void* stream);
+
+/* ---- reconstruction metrics without a pretrained network (csrc/recon_metrics.hip; the reference's metrics notebooks under Generation/ (..._metrics_sub8.ipynb,
+ * Reconstruction_Metrics_ATM.ipynb), which copy MindEye's Reconstruction_Metrics: PixCorr, SSIM, two-way identification).  (ABI 21.)
+ *   eegclip_pixcorr_ssim   a, b: two batches (B, 3, H, W) of planes in EEGCLIP_DT_F32 / _F16 / _BF16, values in [0, 1].  One pass over each pair:
+ *                          pixcorr[i] = Pearson correlation of the 3 H W elements (np.corrcoef(a.ravel(), b.ravel())[0, 1]; moments in fp64; NaN when an
+ *                          image is constant), ssim[i] = skimage's structural_similarity(gaussian_weights=True, sigma=1.5, use_sample_covariance=False,
+ *                          data_range=1) of the rgb2gray images (0.2125 R + 0.7154 G + 0.0721 B): the mean over the (H - 10)(W - 10) pixels whose 11 x 11
+ *                          window lies inside the image, C1 = 1e-4, C2 = 9e-4, fp32 arithmetic about 0.5.  Both fp32 (B).  One workgroup per
+ *                          EEGCLIP_SSIM_TILE_H x EEGCLIP_SSIM_TILE_W tile per pair (smaller tiles while there are fewer workgroups than CUs) writes its
+ *                          partial sums to `workspace` (eegclip_pixcorr_ssim_workspace_bytes(B, H, W) bytes, 8-byte aligned, need not be cleared) and a
+ *                          second launch adds them per pair in a fixed order: no atomics, bit-reproducible.  EEGCLIP_EINVAL: H or W < 11 (or > 2^20),
+ *                          B < 1 or > 65535, an unknown dtype, a workspace too small (the query returns it for a bad shape).  EEGCLIP_EALIGN.
+ *   eegclip_two_way        real, recon: fp32 (N, D) dense rows, N >= 2, D >= 2.  count[j] = #{ i != j : r[i][j] < r[j][j] } (int32 (N)), r[i][j] = Pearson
+ *                          correlation of real[i] with recon[j] (np.corrcoef(real, recon)[:N, N:]); the reference's score is mean(count) / (N - 1).  Row
+ *                          means, centred norms and the diagonal in fp64; the off-diagonal r from exact fp32 products with fp32 accumulation, never stored
+ *                          unless r != NULL (fp32 (N, N)).  workspace: eegclip_two_way_workspace_bytes(N, D) bytes, 4-byte aligned, need not be cleared.
+ *                          Rows are read with 16-byte loads when D % 4 == 0 and both matrices are 16-byte aligned.  EEGCLIP_EINVAL: N < 2 or > 32768,
+ *                          D < 2, a workspace too small.  EEGCLIP_EALIGN: a pointer not aligned to 4 bytes. */
+#define EEGCLIP_SSIM_TILE_H 32
+#define EEGCLIP_SSIM_TILE_W 32
+long long eegclip_pixcorr_ssim_workspace_bytes(int B, int H, int W);
+int eegclip_pixcorr_ssim(const void* a, const void* b, int dtype, int B, int H, int W, float* ssim, float* pixcorr, void* workspace, long long workspace_bytes,
+                         void* stream);
+long long eegclip_two_way_workspace_bytes(int N, int D);
+int eegclip_two_way(const float* real, const float* recon, int N, int D, int* count, float* r, void* workspace, long long workspace_bytes, void* stream);
 
 /* ---- per-kernel timing by the kernel's own GPU timestamps (bench.py roofline): eegclip_time_next_launch(start, stop) arms a pair of
  * library-owned events for the FIRST kernel the calling thread's next entry point launches (hipExtLaunchKernel start / stop events: what
