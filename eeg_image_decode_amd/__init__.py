@@ -10,7 +10,8 @@ __version__ = "0.1.0"
 # the caption decoder's and the low-level encoder's public names, resolved on first use: importing the package itself stays free of torch (build.py imports it before the library exists)
 _LAZY = {"GITCaptioner": "git_caption", "WordPieceDecoder": "git_caption", "caption": "git_caption", "LowLevelEncoder": "low_level", "LowLevelTrainer": "low_level",
          "train_low_level": "low_level", "pixcorr_ssim": "metrics", "pixcorr": "metrics", "ssim": "metrics", "two_way_identification": "metrics",
-         "clip_two_way": "metrics", "reconstruction_metrics": "metrics"}
+         "clip_two_way": "metrics", "reconstruction_metrics": "metrics", "alexnet_two_way": "metrics", "AlexNetFeatures": "metric_nets",
+         "alexnet_preprocess": "preprocess"}
 __all__ = sorted(_LAZY)
 
 

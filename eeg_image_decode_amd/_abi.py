@@ -85,6 +85,12 @@ class Conv16Desc(C.Structure):
                 ("chan_bias", C.c_void_p)]
 
 
+class ConvRelu16Desc(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+                ("N", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
+                ("KS", C.c_int), ("stride", C.c_int), ("pad", C.c_int), ("out_pad", C.c_int), ("dtype", C.c_int)]
+
+
 class Convt16Desc(C.Structure):
     _fields_ = [("in_", C.c_void_p), ("W", C.c_void_p), ("out", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
                 ("N", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int), ("Cin", C.c_int), ("Ho", C.c_int), ("Wo", C.c_int), ("Cout", C.c_int),
@@ -153,7 +159,7 @@ class PlanOp(C.Structure):
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_GRAD = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3 = 0, 1
-ABI_VERSION = 21
+ABI_VERSION = 22
 DT_BF16, DT_F16, DT_F32 = 0, 1, 2
 SRC_U8_HWC, RESIZE_BILINEAR, RESIZE_BICUBIC = 3, 2, 3
 SSIM_TILE_H, SSIM_TILE_W = 32, 32
@@ -323,6 +329,10 @@ PROTOTYPES = {
     "eegclip_pixcorr_ssim": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     "eegclip_two_way_workspace_bytes": [_I, _I],
     "eegclip_two_way": [_P, _P, _I, _I, _P, _P, _P, _L, _P],
+    "eegclip_convrelu16_in_width": [_I],
+    "eegclip_convrelu16": [C.POINTER(ConvRelu16Desc), _P],
+    "eegclip_maxpool16": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "eegclip_pack_nchw16": [_P, _P, _I, _I, _I, _I, _P],
     "eegclip_plan_fn_id": [C.c_char_p],
     "eegclip_plan_events": [_I, C.POINTER(C.c_void_p)],
     "eegclip_plan_events_destroy": [_I, C.POINTER(C.c_void_p)],

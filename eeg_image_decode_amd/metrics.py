@@ -5,10 +5,11 @@ Reconstruction_Metrics): PixCorr, SSIM and two-way identification, on images and
                                       skimage's structural_similarity(gaussian_weights=True, sigma=1.5, use_sample_covariance=False, data_range=1.0) on rgb2gray;
 * two_way_identification(real, recon) mean over j of #{ i != j : r[i, j] < r[j, j] } / (N - 1), r = np.corrcoef(real, recon)[:N, N:], for any feature matrices;
 * clip_two_way(images, recons, tower) the same on the `image_embeds` of a CLIP tower of this package;
-* reconstruction_metrics(...)         the table: {"PixCorr", "SSIM"} and one two-way entry per feature net handed in.
+* alexnet_two_way(images, recons, net) the AlexNet(2) / AlexNet(5) rows: the same on `features.4` / `features.11` of a metric_nets.AlexNetFeatures;
+* reconstruction_metrics(...)         the table: {"PixCorr", "SSIM"}, the two AlexNet rows when a net is given, and one two-way entry per feature net handed in.
 
-The notebooks' AlexNet / InceptionV3 / EfficientNet-B1 / SwAV rows need torchvision's pretrained weights, which this package does not carry: hand any
-callable `images -> features` in as a feature net.
+AlexNet's architecture is carried (metric_nets.py, csrc/metric_nets.hip) with seeded weights: load torchvision's IMAGENET1K_V1 state dict into it for the
+notebooks' rows.  The InceptionV3 / EfficientNet-B1 / SwAV rows stay out: hand any callable `images -> features` in as a feature net.
 
 One difference from the notebooks: they resize with torchvision's Resize(425, BILINEAR) on float tensors; here PIL images, uint8 arrays and float tensors of
 another size go through preprocess.resize_crop_normalize(size, filter="bilinear"), PIL's 8-bit antialiased resize (what Resize does to a PIL image), so the
@@ -115,14 +116,30 @@ def clip_two_way(images, recons, tower, size=224, **kw):
     return two_way_identification(feats[0], feats[1], **kw)
 
 
-def reconstruction_metrics(images, recons, feature_nets=None, size=425, device=None):
-    """the notebooks' table for N pairs: {"PixCorr": mean, "SSIM": mean} plus, per `name: callable` of feature_nets, name: the two-way identification score of
+def alexnet_two_way(images, recons, net, size=256, return_counts=False):
+    """the notebooks' AlexNet(2) and AlexNet(5) rows: {"AlexNet(2)": score, "AlexNet(5)": score}, two-way identification on `features.4` and `features.11` of
+    `net` (a metric_nets.AlexNetFeatures; with torchvision's IMAGENET1K_V1 weights loaded, the notebooks' net).  Both sides go through
+    preprocess.alexnet_preprocess(size) -- float tensors as values in [0, 1] -- and ONE forward each gives both nodes.  return_counts=True: each entry is
+    (score, count (N,) int32 on the device)."""
+    feats = []
+    for x in (images, recons):
+        kw = {"in_range": (0.0, 1.0)} if isinstance(x, torch.Tensor) and x.is_floating_point() else {}
+        feats.append(net(preprocess.alexnet_preprocess(x, size=size, dtype=net.dtype, device=net.device, **kw)))
+    return {row: two_way_identification(feats[0][node], feats[1][node], return_counts=return_counts)
+            for row, node in (("AlexNet(2)", "features.4"), ("AlexNet(5)", "features.11"))}
+
+
+def reconstruction_metrics(images, recons, feature_nets=None, size=425, device=None, alexnet=None):
+    """the notebooks' table for N pairs: {"PixCorr": mean, "SSIM": mean} plus, with alexnet= a metric_nets.AlexNetFeatures, "AlexNet(2)" and "AlexNet(5)"
+    (alexnet_two_way at its default size 256) plus, per `name: callable` of feature_nets, name: the two-way identification score of
     callable(images) against callable(recons) (each an (N, ...) feature tensor on the device; e.g. lambda x: tower(preprocess.clip_image_processor(x)).image_embeds).
-    The AlexNet / Inception / EffNet / SwAV rows of the notebooks are such callables around weights this package does not carry."""
+    The Inception / EffNet / SwAV rows of the notebooks are such callables around nets this package does not carry."""
     pix, ssm = pixcorr_ssim(images, recons, size, device)
     out = {"PixCorr": float(pix.mean()), "SSIM": float(ssm.mean())}
+    if alexnet is not None:
+        out.update(alexnet_two_way(images, recons, alexnet))
     for name, net in (feature_nets or {}).items():
         if name in out:
-            raise EegclipError(f"feature net name {name!r} is taken by an image metric")
+            raise EegclipError(f"feature net name {name!r} is taken by another row of the table")
         out[name] = two_way_identification(net(images), net(recons))
     return out

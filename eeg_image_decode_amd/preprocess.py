@@ -1,11 +1,13 @@
 """Image files' pixels -> the `pixel_values` every image consumer here takes, on the GPU and bit for bit what PIL gives: csrc/image_resize.hip resamples with
 PIL's own 8-bit fixed-point arithmetic (antialiased bicubic / bilinear), keeps a centred crop window and applies the per-channel normalisation, in one launch
-per group of equally sized images.  It is the one operation behind three preprocessors of the reference:
+per group of equally sized images.  It is the one operation behind four preprocessors of the reference:
 
 * open_clip_preprocess   open_clip's transform in front of the ViT-H/14 image tower (Retrieval/eegdatasets_leaveone.py:62-74, :108-135: Resize(224, BICUBIC),
                          CenterCrop(224), ToTensor, Normalize) -- what datasets.image_features_from_files / build_feature_cache feed the tower;
 * clip_image_processor   transformers' CLIPImageProcessor with its defaults (the pipeline's feature_extractor in front of the IP-Adapter's image encoder,
                          Generation/custom_pipeline.py:365-373, and GIT's processor): shortest edge 224 bicubic, centre crop, rescale, normalise;
+* alexnet_preprocess     the metrics notebooks' transform in front of AlexNet (Generation/..._metrics_sub8.ipynb: Resize(256, BILINEAR), Normalize with ImageNet's
+                         mean / std), what metric_nets.AlexNetFeatures takes;
 * vae_preprocess         the low-level script's Resize((512, 512)) + ToTensor in front of vae.encode (Generation/train_vae_latent_512_low_level_no_average.py),
                          bilinear (torchvision's default), to the range the VAE takes (diffusers' VaeImageProcessor.normalize: 2 x - 1).
 
@@ -23,6 +25,7 @@ from . import _abi
 from ._lib import EegclipError, check, lib, raw_stream, require_cuda
 from .clip_vision import CLIP_MEAN, CLIP_STD
 
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 FILTERS = {"bicubic": _abi.RESIZE_BICUBIC, "bilinear": _abi.RESIZE_BILINEAR}
 _OUT_CODES = {torch.float32: _abi.DT_F32, torch.float16: _abi.DT_F16, torch.bfloat16: _abi.DT_BF16}
 _tables = {}           # (in_size, out_size, first, count, filter, device) -> (bounds, coeffs, ksize) on the device
@@ -208,6 +211,13 @@ def clip_image_processor(images, size=224, **kw):
     """transformers' CLIPImageProcessor with its defaults (the IP-Adapter's feature_extractor, GIT's processor): shortest edge `size` bicubic, centre crop
     (size, size), rescale 1 / 255, normalise with CLIP's mean / std"""
     return resize_crop_normalize(images, size, (size, size), "bicubic", CLIP_MEAN, CLIP_STD, 1 / 255, crop_rounding="transformers", **kw)
+
+
+def alexnet_preprocess(images, size=256, **kw):
+    """the metrics notebooks' transform in front of AlexNet: Resize(size, BILINEAR) -- the shortest side becomes `size`, no crop -- and Normalize with
+    ImageNet's mean / std.  The notebooks resize float tensors; this is PIL's 8-bit antialiased resize (what Resize does to a PIL image), so the values can
+    differ from the notebooks' in the last digits, as for metrics.pixcorr_ssim.  A float (B, 3, H, W) batch needs in_range (resize_crop_normalize)."""
+    return resize_crop_normalize(images, size, None, "bilinear", IMAGENET_MEAN, IMAGENET_STD, 1 / 255, **kw)
 
 
 def vae_preprocess(images, size=512, filter="bilinear", out_range=(-1, 1), **kw):

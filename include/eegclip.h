@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 21
+#define EEGCLIP_ABI_VERSION 22
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -1118,6 +1118,39 @@ int eegclip_pixcorr_ssim(const void* a, const void* b, int dtype, int B, int H, 
                          void* stream);
 long long eegclip_two_way_workspace_bytes(int N, int D);
 int eegclip_two_way(const float* real, const float* recon, int N, int D, int* count, float* r, void* workspace, long long workspace_bytes, void* stream);
+
+/* ---- the feature net of the metrics table's AlexNet(2) / AlexNet(5) rows (csrc/metric_nets.hip; the reference's metrics notebooks under Generation/ take
+ * torchvision's alexnet through create_feature_extractor at `features.4` and `features.11`; torchvision/models/alexnet.py:18-32 is the layer list).  (ABI 22.)
+ * Activations are 16-bit (EEGCLIP_DT_F16 / _BF16) PADDED NHWC frames as for eegclip_conv16: [image][H + 2 pad][W + 2 pad][C], the border zero and written by no
+ * launch, `pad` what the layer that READS the frame pads by.  fp32 accumulation, one rounding at the store; no atomics: bit-reproducible.
+ *   eegclip_convrelu16   out[n][y][x][co] = relu(bias[co] + sum_{ky,kx,ci} in[n][y * stride + ky - pad][x * stride + kx - pad][ci] W[co][ky][kx][ci]) on the 16-bit
+ *                        matrix cores (implicit GEMM, the tile loop of eegclip_conv16; N tiles of 128, or of 64 where Cout % 128 != 0; the M tail is masked), for
+ *                        (KS, stride, pad, Cin, Cout) = (11, 4, 2, 3, 64), (5, 1, 2, 64, 192), (3, 1, 1, 192, 384), (3, 1, 1, 384, 256), (3, 1, 1, 256, 256) and any
+ *                        N, Hi, Wi with at least one window; anything else: EEGCLIP_EINVAL.  `in`: the frame [N][Hi + 2 pad][Wi + 2 pad][Cin]; for Cin = 3 the
+ *                        frame eegclip_pack_nchw16 writes, [N][Hi + 4][eegclip_convrelu16_in_width(Wi)][4].  W: [Cout][KS * KS][Cin]; for Cin = 3
+ *                        [Cout][11][64] with element 4 kx + ci of row ky, zero where ci = 3 or kx >= 11.  bias: [Cout], 16-bit.  out: the frame
+ *                        [N][Ho + 2 out_pad][Wo + 2 out_pad][Cout], Ho = (Hi + 2 pad - KS) / stride + 1, 0 <= out_pad <= 2; its interior is written.
+ *                        EEGCLIP_EALIGN: in / W not 16-byte, out / bias not 8-byte aligned.
+ *   eegclip_maxpool16    MaxPool2d(3, 2) (floor mode, no padding) of the frame [N][H + 2 in_pad][W + 2 in_pad][C] into the interior of
+ *                        [N][Ho + 2 out_pad][Wo + 2 out_pad][C], Ho = (H - 3) / 2 + 1; C % 8 == 0, H, W >= 3, pads in 0 .. 2, both frames 16-byte aligned.  The
+ *                        stored pattern is the largest tap's own (the maximum starts from the first tap: correct for negative inputs).
+ *   eegclip_pack_nchw16  x (N, 3, H, W) planes, 16-bit -> the first layer's frame: pixel (y, x) at frame pixel (y + 2, x + 2) as {c0, c1, c2, 0}; the rest of the
+ *                        frame (border, fourth channel's neighbours, the columns up to eegclip_convrelu16_in_width(W)) must be zero and is not written.
+ *                        H, W >= 7.  The first layer's k-tile is the 16 frame pixels x 4 channels from a window's left edge: the 5 pixels right of the window and
+ *                        every fourth channel meet zero WEIGHTS, not zero inputs, so an Inf or NaN pixel there makes that window's outputs NaN although a
+ *                        convolution proper would not read it (finite pixels, such as normalised images, are unaffected). */
+typedef struct {
+    const void* in;
+    const void* W;
+    const void* bias;
+    void* out;
+    int N, Hi, Wi, Cin, Cout;
+    int KS, stride, pad, out_pad, dtype;
+} eegclip_convrelu16_desc;
+int eegclip_convrelu16_in_width(int Wi);
+int eegclip_convrelu16(const eegclip_convrelu16_desc* d, void* stream);
+int eegclip_maxpool16(const void* in, void* out, int N, int H, int W, int C, int in_pad, int out_pad, int dtype, void* stream);
+int eegclip_pack_nchw16(const void* x, void* frame, int N, int H, int W, int dtype, void* stream);
 
 /* ---- per-kernel timing by the kernel's own GPU timestamps (bench.py roofline): eegclip_time_next_launch(start, stop) arms a pair of
  * library-owned events for the FIRST kernel the calling thread's next entry point launches (hipExtLaunchKernel start / stop events: what

@@ -1,0 +1,150 @@
+"""What tests/test_metric_nets_emu.py (product host code on the lane emulator, device "cpu") and tests/test_metric_nets_gpu.py (the MI355X, device "cuda")
+share: eeg_image_decode_amd/metric_nets.py and metrics.alexnet_two_way against tests/metric_nets_ref.py.
+
+The network bound: the relative L2 distance of each node to the fp64 restatement is at most 2 x the yardstick's own -- the same chain in fp32 with the input,
+weights, biases and every layer's output rounded to the dtype, on the same inputs and weights.  That is what any 16-bit implementation pays; the factor 2
+covers a different accumulation order and that two sets of random roundings do not coincide."""
+import numpy as np
+import torch
+
+import metric_nets_ref as R
+import recon_metrics_ref as RM
+
+MARGIN = 2.0
+_refs = {}
+
+
+def net_and_refs(device, H, W, N, dtype):
+    """(net, x on the device, fp64 nodes, yardstick nodes); the references of a shape are computed once and shared"""
+    from eeg_image_decode_amd import metric_nets
+    net = metric_nets.AlexNetFeatures(dtype=dtype, device=device, seed=0)
+    x = R.normalised_images(N, H, W).to(dtype)
+    key = (H, W, N, dtype)
+    if key not in _refs:
+        sd = net.state_dict()
+        _refs[key] = (R.features(x, sd), R.yardstick(x, sd, dtype))
+    return net, x.to(device), _refs[key][0], _refs[key][1]
+
+
+def launches(net, x):
+    """the C-ABI launches of one forward, in order, seen through a proxy in front of the library (metric_nets fetches it per call)"""
+    import eeg_image_decode_amd.metric_nets as MN
+    real, seen = MN.lib, []
+
+    class Recording:
+        def __getattr__(self, name):
+            fn = getattr(real(), name)
+            if name == "eegclip_convrelu16_in_width":         # (host arithmetic, no launch)
+                return fn
+            seen.append(name)
+            return fn
+    MN.lib = lambda: Recording()
+    try:
+        net(x)
+    finally:
+        MN.lib = real
+    return seen
+
+
+def check_features(device, H, W, N, dtype):
+    """both nodes against the fp64 restatement within 2 x the yardstick, the reference's shapes, run-to-run bit identity, the 8 launches of a forward, a batch split into chunks, one node
+    alone, state dict loading.  Returns {node: product error / yardstick error}."""
+    from eeg_image_decode_amd._lib import EegclipError
+    net, x, ref, yard = net_and_refs(device, H, W, N, dtype)
+    got = net(x)
+    assert sorted(got) == ["features.11", "features.4"]
+    ratios = {}
+    for node in ("features.4", "features.11"):
+        g = got[node]
+        assert tuple(g.shape) == tuple(ref[node].shape) and g.dtype == dtype and g.device.type == torch.device(device).type
+        assert g.permute(0, 2, 3, 1).is_contiguous()                     # a permuted view of the NHWC result
+        e, ey = R.rel_l2(g, ref[node]), R.rel_l2(yard[node], ref[node])
+        ratios[node] = e / ey
+        print(f"\n[metric_nets] {H}x{W} N={N} {dtype} {node} {tuple(g.shape)}: rel L2 {e:.2e}, yardstick {ey:.2e}, ratio {e / ey:.2f}", end=" ")
+        assert e <= MARGIN * ey, (node, e, ey)
+        assert float((ref[node] > 0).double().mean()) > 0.05              # (a live node, not a tensor of zeros)
+    for _ in range(2):
+        again = net(x)
+        assert all(torch.equal(again[n], got[n]) for n in got)
+    assert launches(net, x) == ["eegclip_pack_nchw16", "eegclip_convrelu16", "eegclip_maxpool16", "eegclip_convrelu16", "eegclip_maxpool16"] + ["eegclip_convrelu16"] * 3
+    split = net(x, chunk=max(1, N - 1))                                   # two chunks, the second smaller, through the same frames
+    assert all(torch.equal(split[n], got[n]) for n in got)
+    for node in ("features.4", "features.11"):
+        only = net(x, nodes=(node,))
+        assert list(only) == [node] and torch.equal(only[node], got[node])
+    # torchvision's full state dict: the classifier's keys are accepted and dropped; any other key is an error
+    sd = {k: v.clone() for k, v in net.state_dict().items()}
+    assert sorted(sd) == sorted(f"features.{i}.{p}" for i, *_ in R.LAYERS for p in ("weight", "bias"))
+    assert [tuple(sd[f"features.{i}.weight"].shape) for i, *_ in R.LAYERS] == [(cout, cin, k, k) for _, cin, cout, k, _, _ in R.LAYERS]
+    full = dict(sd, **{"classifier.1.weight": torch.zeros(8, 8), "classifier.1.bias": torch.zeros(8), "classifier.6.weight": torch.zeros(4, 8)})
+    full["features.10.bias"] = torch.zeros_like(sd["features.10.bias"])
+    net.load_state_dict(full)
+    zeroed = net(x)["features.11"]
+    assert not torch.equal(zeroed, got["features.11"])                    # (the packed weights and biases follow the load)
+    net.load_state_dict(sd)
+    assert torch.equal(net(x)["features.11"], got["features.11"])
+    for bad in (dict(sd, **{"features.12.weight": torch.zeros(1)}), {k: v for k, v in sd.items() if k != "features.6.bias"}, dict(sd, **{"avgpool.weight": torch.zeros(1)})):
+        try:
+            net.load_state_dict(bad)
+        except RuntimeError:
+            continue
+        raise AssertionError("a wrong key loaded")
+    for bad in (lambda: net(x[:, :, :30]), lambda: net(x[:, :, :, :14], nodes=("features.4",)), lambda: net(x.to(torch.float32)), lambda: net(x, nodes=("features.12",)),
+                lambda: net(x[:, :2])):
+        try:
+            bad()
+        except EegclipError:
+            continue
+        raise AssertionError("no EegclipError")
+    small = net(x[:, :, :15, :16], nodes=("features.4",))["features.4"]   # the smallest input of the shallow node
+    assert tuple(small.shape) == (N, 192, 1, 1)
+    return ratios
+
+
+def two_way_inputs(device, H, W, N, dtype):
+    """-> (images, recons, reference counts per row).  images / recons: R.mixed_pairs as (N, 3, H, W) fp32 in [0, 1] on the device.  The reference is the fp64
+    restatement applied to preprocess.alexnet_preprocess's OWN output at size H (the resize is tested against PIL elsewhere).  From the reference alone, on the
+    CPU: every comparison is away from a tie by 10 x what 16-bit rounding moves r (the yardstick against fp64), and the counts are not all N - 1."""
+    from eeg_image_decode_amd import metric_nets, preprocess as P
+    images, recons = (t.to(device) for t in R.mixed_pairs(N, H, W))
+    sd = metric_nets.AlexNetFeatures(dtype=dtype, device="cpu", seed=0).state_dict()
+    xa, xb = (P.alexnet_preprocess(t, size=H, dtype=dtype, device=device, in_range=(0.0, 1.0)).cpu() for t in (images, recons))
+    assert tuple(xa.shape) == (N, 3, H, W)
+    fa, fb, ya, yb = R.features(xa, sd), R.features(xb, sd), R.yardstick(xa, sd, dtype), R.yardstick(xb, sd, dtype)
+    counts = {}
+    for row, node in (("AlexNet(2)", "features.4"), ("AlexNet(5)", "features.11")):
+        r, count, _ = RM.two_way(fa[node].numpy(), fb[node].numpy())
+        ry, _, _ = RM.two_way(ya[node].double().numpy(), yb[node].double().numpy())
+        gap, moved = RM.two_way_gap(r), float(np.abs(ry - r).max())
+        print(f"\n[metric_nets] {row}: reference counts {count.tolist()}, smallest margin {gap:.1e}, {dtype} rounding moves r by {moved:.1e}", end=" ")
+        assert gap >= 10 * moved, (row, gap, moved)
+        assert not (count == N - 1).all(), (row, count)
+        counts[row] = count
+    return images, recons, counts
+
+
+def check_two_way_rows(device, H, W, N):
+    """metrics.alexnet_two_way in fp16 at H x W (size=H: no resize): the counts of both rows are the reference's, every comparison included"""
+    from eeg_image_decode_amd import metric_nets, metrics as M
+    images, recons, counts = two_way_inputs(device, H, W, N, torch.float16)
+    net = metric_nets.AlexNetFeatures(dtype=torch.float16, device=device, seed=0)
+    out = M.alexnet_two_way(images, recons, net, size=H, return_counts=True)
+    assert sorted(out) == ["AlexNet(2)", "AlexNet(5)"]
+    for row, (score, count) in out.items():
+        assert count.dtype == torch.int32 and np.array_equal(count.cpu().numpy(), counts[row]), (row, count.tolist(), counts[row].tolist())
+        assert abs(score - counts[row].mean() / (N - 1)) < 1e-12
+    plain = M.alexnet_two_way(images, recons, net, size=H)
+    assert plain == {row: out[row][0] for row in out}
+    return images, recons, net
+
+
+def check_table(device, images, recons, net, size):
+    """metrics.reconstruction_metrics(..., alexnet=net): the four keys, the AlexNet rows are alexnet_two_way's at its default size, and PixCorr / SSIM are
+    those of the call without a net"""
+    from eeg_image_decode_amd import metrics as M
+    base = M.reconstruction_metrics(images, recons, size=size, device=device)
+    out = M.reconstruction_metrics(images, recons, size=size, device=device, alexnet=net)
+    assert sorted(base) == ["PixCorr", "SSIM"] and sorted(out) == ["AlexNet(2)", "AlexNet(5)", "PixCorr", "SSIM"]
+    assert out["PixCorr"] == base["PixCorr"] and out["SSIM"] == base["SSIM"]
+    rows = M.alexnet_two_way(images, recons, net)
+    assert all(isinstance(out[k], float) and out[k] == rows[k] for k in rows)
