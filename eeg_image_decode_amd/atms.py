@@ -347,10 +347,9 @@ def _dp_world():
 
 def _head_split(B):
     """split-K factor of the projection-head GEMMs (M = B is small: a 4 x 16 tile grid cannot fill 256 CUs).  Every slice adds its
-    partial tile with atomics, so the factor trades workgroups against B * 1024 * split float atomics."""
-    import os
-    cap = int(os.environ.get("EEGCLIP_HEAD_SK", "8"))        # tuning aid; measured at B = 256: 16 -> 101 us, 8 -> 80 us, 4 -> 103 us for the four GEMMs
-    return max(1, min(cap, 2048 // max(1, ((B + 63) // 64) * (P_DIM // 64))))
+    partial tile with atomics, so the factor trades workgroups against B * 1024 * split float atomics.  The cap of 8 was measured at B = 256:
+    16 -> 101 us, 8 -> 80 us, 4 -> 103 us for the four GEMMs."""
+    return max(1, min(8, 2048 // max(1, ((B + 63) // 64) * (P_DIM // 64))))
 
 
 class _Engine:
@@ -424,8 +423,8 @@ class _Engine:
 
     def _head_planes_enabled(self, pl):
         """the projection head (and, in the step plan / ClipLoss, the query gradient) on the K-parallel plane GEMM csrc/head_gemm.hip (round 6) in split-bf16
-        plans; EEGCLIP_HEAD_GEMM=0 pins round 5's split-K gemm_x3 launches (diagnosis, A/B timing); exact-fp32 plans always use those"""
-        return pl.precision == _abi.PREC_BF16X3 and os.environ.get("EEGCLIP_HEAD_GEMM", "1") != "0"
+        plans; exact-fp32 plans keep the split-K fp32-operand GEMM launches"""
+        return pl.precision == _abi.PREC_BF16X3
 
     def _head_weight_planes(self):
         """bf16 hi | lo planes of this step's projection-head weights: the span [W1 | b1 | W2] as it lies in the flat parameter buffer, ONE dense split.  The
@@ -563,7 +562,7 @@ class _Engine:
             # nothing before the conv stack needs it: the arena clear goes to the second stream, under the transformer block; the main stream joins in front of
             # the conv stack.  (The lean plans have nothing to clear.)
             if not lean:
-                pl.memset(b["zfb"] if train else b["zf"], side=os.environ.get("EEGCLIP_START_SIDE", "1") != "0")
+                pl.memset(b["zfb"] if train else b["zf"], side=True)
                 pl.clears_zb = train
             if not hasattr(self, "cs_packed"):
                 self.cs_packed = torch.empty(int(lib().eegclip_cstack_packed_bytes(N_CH)) // 2, dtype=torch.bfloat16, device=self.device)
@@ -705,17 +704,11 @@ class _Engine:
             # each slice leaves its partial tile as a slab and the launch that consumes the result anyway adds the slabs while it loads them:
             # bias + GELU (+ the planes of gelu(u) for the second Linear) after the first, dropout + residual + LayerNorm after the second
             fp, gp = (_p(b["featp"][0]), _p(b["featp"][1])), (_p(b["gup"][0]), _p(b["gup"][1]))
-            # (OPT-IN EEGCLIP_HEAD_FUSED_EPI=1: the first Linear unsplit with bias + GELU + planes in its own epilogue -- one launch instead of GEMM slabs +
-            #  head_act; measured SLOWER in the step, 0.658 - 0.661 against 0.647 - 0.655 ms alternated in one call (34 launches against 36): the unsplit GEMM walks
-            #  K alone for 13 us where the K-parallel GEMM + the elementwise launch take 6.5 + 6)
-            fused_epi = os.environ.get("EEGCLIP_HEAD_FUSED_EPI", "0") == "1"
-            if fused_epi:
-                pl.call_desc("eegclip_head_gemm", _abi.HeadGemmDesc(a_hi=fp[0], a_lo=fp[1], b_hi=self.hw["w1"][0], b_lo=self.hw["w1"][1], lda=F_TS, ldb=F_TS, M=B,
-                                                                   N=P_DIM, K=F_TS, slices=1, slab_stride=0, bias=_p(P["proj_eeg.0.bias"]), Cpre=_p(b["u"]),
-                                                                   ldcpre=P_DIM, act=ACT_GELU, C=_p(b["gu"]), ldc=P_DIM, p_hi=gp[0], p_lo=gp[1], ldp=P_DIM))
-            else:
-                sl1 = self._head_gemm(pl, b, "hslab1", fp, F_TS, self.hw["w1"], P_DIM, B)
-                pl.call("eegclip_head_act", *sl1, _p(P["proj_eeg.0.bias"]), _p(b["u"]), _p(b["gu"]), *gp, B, P_DIM)
+            # (the first Linear unsplit with bias + GELU + planes in its own epilogue -- one launch instead of GEMM slabs + head_act -- measured SLOWER in the
+            #  step, 0.658 - 0.661 against 0.647 - 0.655 ms alternated in one call: the unsplit GEMM walks K alone for 13 us where the K-parallel GEMM + the
+            #  elementwise launch take 6.5 + 6)
+            sl1 = self._head_gemm(pl, b, "hslab1", fp, F_TS, self.hw["w1"], P_DIM, B)
+            pl.call("eegclip_head_act", *sl1, _p(P["proj_eeg.0.bias"]), _p(b["u"]), _p(b["gu"]), *gp, B, P_DIM)
             sl2 = self._head_gemm(pl, b, "hslab2", gp, P_DIM, self.hw["w2"], P_DIM, B)
             # s = u + dropout(W gelu(u) + b), out = LayerNorm(s): ResidualAdd + LayerNorm of Proj_eeg in one launch; `out` is a fresh tensor per call
             # (argument 8 is patched by forward()); arguments 19 / 20: out again as planes (the step plan's loss operand)
@@ -724,7 +717,7 @@ class _Engine:
                     _p(P["proj_eeg.2.bias"]), 0, _p(b["mu4"]), _p(b["rs4"]), None, None, None, None, None, B, P_DIM, EPS, None, None, sl2[1], sl2[2],
                     _p(P["proj_eeg.1.fn.1.bias"]), seed_at=4)
             return pl
-        # A6 on fp32 operands (exact-fp32 plans, EEGCLIP_HEAD_GEMM=0): a 4 x 16 tile grid cannot fill 256 CUs and each workgroup walks K = 1440
+        # A6 on fp32 operands (exact-fp32 plans): a 4 x 16 tile grid cannot fill 256 CUs and each workgroup walks K = 1440
         # serially, so the products are split over K (atomics into a zeroed buffer) and bias/GELU/dropout/residual run as a tiny epilogue.
         skh = _head_split(B)
         if skh > 1:
@@ -837,22 +830,18 @@ class _Engine:
         sums, bn = b["sums"], b["bn"]
         # the small parameter-gradient reductions (conv taps, the block's LayerNorm rows) wait for the end of the backward and go to the second stream behind
         # ONE fork with the token-row gradient: a fork costs the main stream 4 - 13 us of idle queue (tools/step_timeline.py), as much as each of them runs
-        defer_small = os.environ.get("EEGCLIP_DEFER_SMALL", "1") != "0"
         pl.deferred = []
-        wsk = int(os.environ.get("EEGCLIP_WGRAD_SK", "0"))                         # tuning aid: K-slice count of the long-K weight gradients
         # attention backward: split-bf16 products (csrc/attention_x3.hip) in plans whose GEMM precision is bf16x3, the exact-fp32 MFMA kernel otherwise
         attn_bwd = "eegclip_attention_bwd_x3" if pl.precision == _abi.PREC_BF16X3 else "eegclip_attention_bwd"
-        sk = lambda k: (wsk if (wsk > 0 and k >= 4096) else max(1, min(64, k // 512)))      # split-K for the reduce-over-batch weight-gradient GEMMs
+        sk = lambda k: max(1, min(64, k // 512))      # split-K for the reduce-over-batch weight-gradient GEMMs
 
-        head_side = os.environ.get("EEGCLIP_HEAD_WGRAD_SIDE", "1") != "0"      # (A/B aid)
-
-        def wgrad(name, dY, ldy, X, ldx, Nout, Nin, K, bias=None, side=head_side):
+        def wgrad(name, dY, ldy, X, ldx, Nout, Nin, K, bias=None, side=True):
             """G[name] (Nout, Nin) += dY^T X   with dY (K, ldy), X (K, ldx) row-major; bias: G[bias] (Nout) += column sums of dY, taken
             from the A tiles the same launch stages (rowsum_a) instead of a separate pass over dY"""
             return pl.gemm(Nout, Nin, K, dY, D(1), D(ldy), X, D(ldx), D(1), _p(G[name]), D(Nin), D(1), accumulate=1, split_k=sk(K),
                            rowsum_a=_p(G[bias]) if bias else None, side=side)    # nobody reads a weight gradient before the optimizer
 
-        ln_side = os.environ.get("EEGCLIP_LN_SIDE", "1") != "0"           # LayerNorm parameter-gradient kernels on the second stream (A/B aid)
+        # (the LayerNorm parameter-gradient kernels run on the second stream)
         # the three token-block LayerNorms reduce their gamma / beta gradients through per-workgroup partial rows (one workspace: the three launches
         # are ordered on one stream) instead of 256-way contended atomics
         if "lnp_ws" not in b:
@@ -868,6 +857,7 @@ class _Engine:
         head_planes = self._head_planes_enabled(pl) and hasattr(self, "hw")
         pl.head_planes = head_planes
         dfeat_slabs = None
+        head_side_ops = []
         if head_planes:
             # (round 6) the head's backward on the K-parallel plane GEMM.  The upstream gradient may itself be the partial slabs of the loss's query-gradient
             # GEMM (arguments 1 / 2, patched by the step plan); the LayerNorm backward leaves ds, dv = ds * mask / (1 - p) (fp32: the weight gradients'
@@ -881,33 +871,21 @@ class _Engine:
                     _p(b["dv"]), *vp, None, pp_, 0, SITE_PROJ, seed_at=15)
             # the head's second-stream launches (LayerNorm parameter half, the two weight gradients: operands dv | gu and du | feat stay untouched until the
             # optimizer) are emitted TOGETHER in front of the conv stack's backward, next to its own second-stream launch: ONE fork instead of three -- every
-            # fork idles the main queue for ~7 us (tools/step_timeline.py).  EEGCLIP_HEAD_FORKS=3: each as soon as its operands exist (A/B aid)
-            one_fork = os.environ.get("EEGCLIP_HEAD_FORKS", "1") == "1"
-            head_side_ops = []
-
-            def later(fn):
-                if one_fork:
-                    head_side_ops.append(fn)
-                else:
-                    fn()
+            # fork idles the main queue for ~7 us (tools/step_timeline.py)
+            later = head_side_ops.append
 
             def ln_params():
                 pl.dout_par_op = len(pl.ops)
                 pl.call("eegclip_layernorm_bwd", 0, _p(b["s"]), None, _p(b["mu4"]), _p(b["rs4"]), None,
-                        _p(G["proj_eeg.2.weight"]), _p(G["proj_eeg.2.bias"]), B, P_DIM, 0, None, 0.0, 0, 0, side=ln_side)
+                        _p(G["proj_eeg.2.weight"]), _p(G["proj_eeg.2.bias"]), B, P_DIM, 0, None, 0.0, 0, 0, side=True)
             later(ln_params)
             # both weight gradients of the head from the planes that exist anyway (dv | gelu(u), du | feat: every operand row-major, contraction over the batch
             # rows) in ONE eegclip_wgrad_planes launch -- the fp32-operand GEMMs (k-strided operands) took 30 + 37 us alone and far longer beside the backward
-            wplanes = B % 32 == 0 and os.environ.get("EEGCLIP_HEAD_WGRAD_PLANES", "1") != "0"
+            wplanes = B % 32 == 0
             if not wplanes:
                 later(lambda: wgrad("proj_eeg.1.fn.1.weight", _p(b["dv"]), P_DIM, _p(b["gu"]), P_DIM, P_DIM, P_DIM, B, bias="proj_eeg.1.fn.1.bias"))
-            if os.environ.get("EEGCLIP_HEAD_FUSED_EPI", "0") == "1":     # (opt-in, see the forward: GELU' + the residual in the unsplit GEMM's epilogue)
-                pl.call_desc("eegclip_head_gemm", _abi.HeadGemmDesc(a_hi=vp[0], a_lo=vp[1], b_hi=self.hw["w2"][0], b_lo=self.hw["w2"][1], lda=P_DIM, ldb=P_DIM, M=B,
-                                                                   N=P_DIM, K=P_DIM, slices=1, slab_stride=0, act=ACT_GELU_GRAD, aux=_p(b["u"]), ldaux=P_DIM,
-                                                                   R=_p(b["ds"]), ldr=P_DIM, C=_p(b["ds"]), ldc=P_DIM, p_hi=up[0], p_lo=up[1], ldp=P_DIM, b_kmajor=1))
-            else:
-                sl = self._head_gemm(pl, b, "dgu_slabs", vp, P_DIM, self.hw["w2"], P_DIM, B, kmajor=True)
-                pl.call("eegclip_head_act_bwd", *sl, _p(b["u"]), _p(b["ds"]), _p(b["ds"]), *up, B * P_DIM)          # ds := du = ds + dgu * gelu'(u)
+            sl = self._head_gemm(pl, b, "dgu_slabs", vp, P_DIM, self.hw["w2"], P_DIM, B, kmajor=True)
+            pl.call("eegclip_head_act_bwd", *sl, _p(b["u"]), _p(b["ds"]), _p(b["ds"]), *up, B * P_DIM)          # ds := du = ds + dgu * gelu'(u)
             if wplanes:
                 gp_, fp_ = (_p(b["gup"][0]), _p(b["gup"][1])), (_p(b["featp"][0]), _p(b["featp"][1]))
                 probs = (_abi.WgradPlanesProblem * 2)(
@@ -916,13 +894,12 @@ class _Engine:
                     _abi.WgradPlanesProblem(a_hi=up[0], a_lo=up[1], lda=P_DIM, b_hi=fp_[0], b_lo=fp_[1], ldb=F_TS, rows=B, M=P_DIM, N=F_TS,
                                             out=_p(G["proj_eeg.0.weight"]), ldo=F_TS, bias_out=_p(G["proj_eeg.0.bias"]), slices=1))
                 pl._keep.append(probs)
-                later(lambda: pl.call("eegclip_wgrad_planes", probs, 2, side=head_side))
+                later(lambda: pl.call("eegclip_wgrad_planes", probs, 2, side=True))
             else:
                 later(lambda: wgrad("proj_eeg.0.weight", _p(b["ds"]), P_DIM, _p(b["feat"]), F_TS, P_DIM, F_TS, B, bias="proj_eeg.0.bias"))
             dfeat_slabs = self._head_gemm(pl, b, "dfeat_slabs", up, P_DIM, self.hw["w1"], F_TS, B, kmajor=True)
         else:
-            head_side_ops = []
-            self._build_bwd_head_f32(pl, b, B, pp_, ln_side, wgrad)
+            self._build_bwd_head_f32(pl, b, B, pp_, wgrad)
         # 1x1 conv backward + BatchNorm2 / ELU / dropout backward statistics in one launch (dW, dbias, dz2, sums[2]); then -- after the SyncBN
         # all-reduce of the sums under torch.distributed -- the apply pass.  dgamma / dbeta take this rank's LOCAL sums, so the later
         # mean-all-reduce of the flat gradient (every rank's gradient is W x its share) reproduces the single-process value.
@@ -981,7 +958,7 @@ class _Engine:
             for f in head_side_ops:
                 f()
         if self._cstack_bwd_enabled(pl):
-            self._build_bwd_cstack(pl, b, B, train, W, zsum, conv_bias_grad if not train else None, early_reduce, defer_small)
+            self._build_bwd_cstack(pl, b, B, train, W, zsum, conv_bias_grad if not train else None, early_reduce)
         else:
             self._build_bwd_conv_y1(pl, b, B, train, W, zsum, conv_bias_grad if not train else None, early_reduce)
         fused = self._token_block_enabled(pl) and hasattr(self, "tb_packed")
@@ -1013,7 +990,7 @@ class _Engine:
                     arr[i] = _abi.WgradTokProblem(a=a, b=x, a_group_stride=B * 65536 if mg > 1 else 0, m_groups=mg, heads_m=hm, heads_n=hn, M=M, N=N,
                                                   out=_p(G[name]), ldo=N, bias_out=_p(G[bias]) if bias else None, bias_mfma=bm, sample_index=index)
                 groups = sum(q[2] for q in problems)
-                slices = slices or (wsk if wsk > 0 else int(lib().eegclip_wgrad_tok_slices(groups, B)))
+                slices = slices or int(lib().eegclip_wgrad_tok_slices(groups, B))
                 key = "wk:" + tag
                 if key not in b:
                     b[key] = torch.empty(int(lib().eegclip_wgrad_tok_workspace_floats(arr, len(problems), B, slices)), dtype=torch.float32, device=self.device)
@@ -1023,33 +1000,19 @@ class _Engine:
                 pl.call("eegclip_wgrad_tok_reduce", arr, len(problems), B, slices, _p(b[key]), side=side)
                 return arr, ops
 
-            # EEGCLIP_WGRAD_MERGE: 0 = three weight-gradient launches, each as soon as its dY planes exist (second stream);
-            # 1 = the q | k | v gradient waits for the embedding's and shares its launch; 2 = all five in ONE launch after the last dY (joint-subject model: the
-            # four shared ones in one launch, the per-subject value embeddings in theirs).  The fused backward
+            # all five weight gradients of the block wait for the last dY and run as ONE launch (joint-subject model: the four shared ones in one launch,
+            # the per-subject value embeddings in theirs), not each as soon as its dY planes exist.  The fused backward
             # kernels own their CUs (160 KB of LDS, 2 waves per SIMD of 200+ VGPRs), so an "overlapping" weight-gradient launch in fact queues for CUs behind
             # them: fewer, fuller launches read the same 192 MB of planes with more workgroups in flight
-            merge = int(os.environ.get("EEGCLIP_WGRAD_MERGE", "2"))
-            late = []
-            ffn_out = [
+            late = [
                 (_LY + "conv2.weight", df2p, 1, g1p, D_MODEL, D_FF, 0, 0, _LY + "conv2.bias", 1),          # g1 has 256 real channels: no ones column
                 (_LY + "conv1.weight", dg1p, 1, n1p, D_FF, D_MODEL, 0, 0, _LY + "conv1.bias", 0),
-                (_LY + "attention.out_projection.weight", da1p, 1, ctxp, D_MODEL, HE, 0, 1, _LY + "attention.out_projection.bias", 0)]
-            qkv_w = [(_LY + "attention.query_projection.weight", dqkvp, 3, hp, 3 * HE, D_MODEL, 1, 0, _LY + "attention.query_projection.bias", 0)]
+                (_LY + "attention.out_projection.weight", da1p, 1, ctxp, D_MODEL, HE, 0, 1, _LY + "attention.out_projection.bias", 0),
+                (_LY + "attention.query_projection.weight", dqkvp, 3, hp, 3 * HE, D_MODEL, 1, 0, _LY + "attention.query_projection.bias", 0)]
             pl.call("eegclip_token_block_bwd", ctypes.byref(bd), 0)
-            if defer_small:
-                pl.deferred.append(lambda: pl.call("eegclip_token_block_bwd", ctypes.byref(bd), 2, side=True))
-            else:
-                pl.call("eegclip_token_block_bwd", ctypes.byref(bd), 2, side=ln_side)
-            if merge >= 2:
-                late += ffn_out
-            else:
-                wgrad_tok("ffn_out", ffn_out)
+            pl.deferred.append(lambda: pl.call("eegclip_token_block_bwd", ctypes.byref(bd), 2, side=True))
             pl.call(attn_bwd, _p(b["qkv"]), _p(b["dctx"]), dqkvp, 1, B, L_TOK, N_HEADS, D_HEAD, 3 * HE, 1.0 / math.sqrt(D_HEAD),
                     pe_, 0, SITE_ATTN, seed_at=11)
-            if merge >= 1:
-                late += qkv_w
-            else:
-                wgrad_tok("qkv", qkv_w)
             pl.call("eegclip_token_block_bwd", ctypes.byref(bd), 1)
         else:
             # final LN, LN2
@@ -1100,14 +1063,13 @@ class _Engine:
             # value embedding: dY = the token-row gradients part 1 left as planes, X = the EEG sample planes of the forward (row 0 zero: the subject
             # token has no EEG row; ones column in rows 1..63: bias gradient = sum of the 63 channel rows of every sample)
             if not self.joint:
-                wgrad_tok("embed" + ("+%d" % len(late) if late else ""), late + [(_E + "value_embedding.weight", dr1p, 1, xp, D_MODEL, T_LEN, 0, 0, _E + "value_embedding.bias", 0)], side=False)
+                wgrad_tok("block+embed", late + [(_E + "value_embedding.weight", dr1p, 1, xp, D_MODEL, T_LEN, 0, 0, _E + "value_embedding.bias", 0)], side=False)
             else:
                 # joint-subject model: one problem per subject PRESENT in the batch, each contracting over that subject's samples only -- a range of
                 # the subject-ordered sample list b["perm"] (the planes stay in batch order: the kernel looks the sample up per k-tile).  The member
                 # problems, their count and sample ranges are patched per call (_joint_layout); absent subjects get no gradient (their .grad stays
                 # None as in the reference, Embed.py:142-144).
-                if late:
-                    wgrad_tok("block", late, side=False)
+                wgrad_tok("block", late, side=False)
                 pl.j_wk_template = [(w, dr1p, 1, xp, D_MODEL, T_LEN, 0, 0, bk, 0) for w, bk in self.ve_keys]
                 # K slices per subject so that (subjects present) x 4 tiles x slices fills the chip: 32 for one subject .. 6 for ten; the workspace takes
                 # the largest product
@@ -1149,8 +1111,8 @@ class _Engine:
                 pl.call("eegclip_gather_rows", _p(b["dx"]), XR, _p(b["dxs"]), XR, _p(b["perm"]), B, XR, 1)
         return pl
 
-    def _build_bwd_head_f32(self, pl, b, B, pp_, ln_side, wgrad):
-        """the projection head's backward on fp32-operand GEMMs (exact-fp32 plans, EEGCLIP_HEAD_GEMM=0): split-K with atomics into the cleared arena"""
+    def _build_bwd_head_f32(self, pl, b, B, pp_, wgrad):
+        """the projection head's backward on fp32-operand GEMMs (exact-fp32 plans): split-K with atomics into the cleared arena"""
         P, G = self.P, self.G
         # s = u + dropout(W4 gelu(u) + b4): the LayerNorm backward writes ds and dv = ds * mask / (1 - p) in one pass
         pl.call("eegclip_layernorm_bwd", 0, _p(b["s"]), _p(P["proj_eeg.2.weight"]), _p(b["mu4"]), _p(b["rs4"]), _p(b["ds"]),
@@ -1158,7 +1120,7 @@ class _Engine:
         # (the gamma / beta gradients of every LayerNorm are a second, independent kernel: it runs on the side stream, off the dX chain)
         pl.dout_par_op = len(pl.ops)
         pl.call("eegclip_layernorm_bwd", 0, _p(b["s"]), None, _p(b["mu4"]), _p(b["rs4"]), None,
-                _p(G["proj_eeg.2.weight"]), _p(G["proj_eeg.2.bias"]), B, P_DIM, 0, None, 0.0, 0, 0, side=ln_side)
+                _p(G["proj_eeg.2.weight"]), _p(G["proj_eeg.2.bias"]), B, P_DIM, 0, None, 0.0, 0, 0, side=True)
         wgrad("proj_eeg.1.fn.1.weight", _p(b["dv"]), P_DIM, _p(b["gu"]), P_DIM, P_DIM, P_DIM, B, bias="proj_eeg.1.fn.1.bias")
         skh = _head_split(B)
         pl.gemm(B, P_DIM, P_DIM, _p(b["dv"]), D(P_DIM), D(1), _p(P["proj_eeg.1.fn.1.weight"]), D(P_DIM), D(1), _p(b["dgu"]), D(P_DIM), D(1),
@@ -1168,7 +1130,7 @@ class _Engine:
         pl.gemm(B, F_TS, P_DIM, _p(b["ds"]), D(P_DIM), D(1), _p(P["proj_eeg.0.weight"]), D(F_TS), D(1), _p(b["dfeat"]), D(F_TS), D(1),
                 accumulate=int(skh > 1), split_k=skh)
 
-    def _build_bwd_cstack(self, pl, b, B, train, W, zsum, conv_bias_grad, early_reduce, defer_small=False):
+    def _build_bwd_cstack(self, pl, b, B, train, W, zsum, conv_bias_grad, early_reduce):
         """spatial conv + BN1 + ELU + temporal conv backward recomputed from the token rows (csrc/cstack_bwd.hip, round 5): y1 / z1 / dz1 / dy1 never
         exist in HBM.  dWs on the second stream; BatchNorm1-backward sums as one partial row per sample, summed in a fixed order by the apply pass."""
         P, G, sums, bn = self.P, self.G, b["sums"], b["bn"]
@@ -1180,7 +1142,7 @@ class _Engine:
         xs = (_p(b["n3"]), L_TOK * D_MODEL, D_MODEL)
         bnp = (_p(bn[0]), _p(bn[1]), _p(P[_TS + "2.weight"]), _p(P[_TS + "2.bias"]))
         pl.call("eegclip_cstack_bwd_w2", *xs, _p(P[_TS + "0.weight"]), _p(P[_TS + "0.bias"]), *bnp, _p(b["dy2"]), _p(G[_TS + "4.weight"]), _p(b["csw_ws"]),
-                B, N_CH, side=os.environ.get("EEGCLIP_W2_SIDE", "1") != "0")
+                B, N_CH, side=True)
         rows3 = b["cs_rows3"]
         count1 = float(W * B * N_CH * W_TS)
         common = dict(B=B, H=N_CH, x=xs[0], xs_b=xs[1], xs_h=xs[2], w25=_p(P[_TS + "0.weight"]), bias1=_p(P[_TS + "0.bias"]), mean1=bnp[0], rstd1=bnp[1],
@@ -1204,7 +1166,7 @@ class _Engine:
         def taps():
             pl.taps_op = len(pl.ops)
             pl.call("eegclip_cstack_bwd_taps_reduce", _p(b["csb_ws"]), B, _p(G[_TS + "0.weight"]), side=True)
-        if early_reduce or not defer_small:
+        if early_reduce:
             taps()
         else:
             pl.deferred.append(taps)          # with the other small reductions, behind ONE fork at the end of the backward (see _build_bwd)

@@ -196,40 +196,31 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(const ca_args a) {
     }
 }
 
-// ---- SDXL's own shape (77 text tokens = 5 key tiles, 0 or 4 image tokens = 0 / 1 tile): K and V^T fragments live in REGISTERS -----------
-// A wave walks 8 query tiles against the same keys.  Re-reading the K / V^T fragments from LDS for every tile cost 28 LDS instructions and
+// ---- SDXL's own shape (77 text tokens = 5 key tiles, 0 or 4 image tokens = 0 / 1 tile): K fragments live in REGISTERS -------------------
+// A wave walks 8 query tiles against the same keys.  Re-reading the K fragments from LDS for every tile cost LDS instructions and
 // their address arithmetic per tile on top of a VALU-heavy softmax (wave64 VALU issues over 4 cycles: ~400 instructions per tile were
-// ~27 us of the 66 us launch, the MFMAs 7.5 us, the HBM roofline 28 us).  With the tile counts as template parameters the fragments are
-// loaded once per wave (112 VGPRs) and the tile loop touches LDS not at all.
+// ~27 us of the 66 us launch, the MFMAs 7.5 us, the HBM roofline 28 us).  With the tile counts as template parameters the K fragments are
+// loaded once per wave; the V^T fragments stay in LDS (in registers as well: measured slower, 2 waves per SIMD instead of 3).
 template <int NT>
 struct kv_frag {
     bf16x8 k[NT > 0 ? NT : 1][2];
-    bf16x8 v[NT > 0 ? (NT + 1) / 2 : 1][4];
+    bf16x8 v[NT > 0 ? (NT + 1) / 2 : 1][4];   // never touched (V^T stays in LDS).  Kept: without it the NT_IP = 0 kernels come out with another register
+                                              // allocation (the unused kv_frag<0> changes size) -- to go with the next change that re-measures them
 };
 
-template <int NT, bool VREG>
-__device__ __forceinline__ void load_frag(kv_frag<NT>& f, const unsigned short* Ks, const unsigned short* Vt, int ldv, int lane) {
+template <int NT>
+__device__ __forceinline__ void load_frag(kv_frag<NT>& f, const unsigned short* Ks, int lane) {
     const int fr = lane & 15, g = lane >> 4;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int st = 0; st < 2; ++st) f.k[t][st] = *reinterpret_cast<const bf16x8*>(Ks + (16 * t + fr) * CA_KLD + 32 * st + 8 * g);
-    if (!VREG) return;
-#pragma unroll
-    for (int u = 0; u < (NT + 1) / 2; ++u)
-#pragma unroll
-        for (int dn = 0; dn < 4; ++dn) {
-            const unsigned short* vp = Vt + (16 * dn + fr) * ldv + 32 * u + 4 * g;
-            const uint2 lo = *reinterpret_cast<const uint2*>(vp);
-            const uint2 hi = *reinterpret_cast<const uint2*>(vp + 16);
-            f.v[u][dn] = __builtin_bit_cast(bf16x8, (u32x4{lo.x, lo.y, hi.x, hi.y}));
-        }
 }
 
 // same arithmetic, in the same order, as branch() -- the two are interchangeable bit for bit.  TWO query tiles advance in lockstep through
 // every phase (scores, max, exp, sum, P V): the phases of one tile are a dependent chain through MFMA results and cross-lane shuffles, and
 // at 2 waves per SIMD nothing else hides those latencies.
-template <bool F16, int NT, bool VREG>
+template <bool F16, int NT>
 __device__ __forceinline__ void branch_reg2(const kv_frag<NT>& f, const unsigned short* Vt, int ldv, int S, const bf16x8 (&bq)[2][2], float scale2,
                                             float pscale, f32x4 (&acc)[2][4], int lane) {
     const int g = lane >> 4, fr = lane & 15;
@@ -284,23 +275,18 @@ __device__ __forceinline__ void branch_reg2(const kv_frag<NT>& f, const unsigned
         }
 #pragma unroll
         for (int dn = 0; dn < 4; ++dn) {
-            bf16x8 bv;
-            if (VREG) {
-                bv = f.v[u][dn];
-            } else {                                     // V^T fragment from LDS, shared by the two tiles
-                const unsigned short* vp = Vt + (16 * dn + fr) * ldv + 32 * u + 4 * g;
-                const uint2 lo = *reinterpret_cast<const uint2*>(vp);
-                const uint2 hi = *reinterpret_cast<const uint2*>(vp + 16);
-                bv = __builtin_bit_cast(bf16x8, (u32x4{lo.x, lo.y, hi.x, hi.y}));
-            }
+            const unsigned short* vp = Vt + (16 * dn + fr) * ldv + 32 * u + 4 * g;      // V^T fragment from LDS, shared by the two tiles
+            const uint2 lo = *reinterpret_cast<const uint2*>(vp);
+            const uint2 hi = *reinterpret_cast<const uint2*>(vp + 16);
+            const bf16x8 bv = __builtin_bit_cast(bf16x8, (u32x4{lo.x, lo.y, hi.x, hi.y}));
 #pragma unroll
             for (int p = 0; p < 2; ++p) acc[p][dn] = mma<F16>(bv, pa[p], acc[p][dn]);
         }
     }
 }
 
-template <bool F16, int NT, int NT_IP, bool VREG>
-__global__ __launch_bounds__(256, VREG ? 2 : 3) void cross_attn_reg_kernel(const ca_args a) {
+template <bool F16, int NT, int NT_IP>
+__global__ __launch_bounds__(256, 3) void cross_attn_reg_kernel(const ca_args a) {
     EEG_LDS_BASE(unsigned short, lds);
     const int ldv = ca_ldv(NT), ldv_ip = ca_ldv(NT_IP);
     unsigned short* Ks = lds;
@@ -322,8 +308,8 @@ __global__ __launch_bounds__(256, VREG ? 2 : 3) void cross_attn_reg_kernel(const
     const int fr = lane & 15, g = lane >> 4;
     kv_frag<NT> ft;
     kv_frag<NT_IP> fi;
-    load_frag<NT, VREG>(ft, Ks, Vt, ldv, lane);
-    if (NT_IP > 0) load_frag<NT_IP, VREG>(fi, Kip, Vip, ldv_ip, lane);
+    load_frag<NT>(ft, Ks, lane);
+    if (NT_IP > 0) load_frag<NT_IP>(fi, Kip, lane);
     // a wave owns query tiles (it*4 + wave), it = 0..7, taken two at a time (it, it + 1); rows beyond HW are clamped on load, skipped on store
     auto q_ptr = [&](int it) {
         const int qrow = blockIdx.x * CA_QB + (it * 4 + wave) * 16 + fr;
@@ -351,9 +337,9 @@ __global__ __launch_bounds__(256, VREG ? 2 : 3) void cross_attn_reg_kernel(const
         for (int p = 0; p < 2; ++p)
 #pragma unroll
             for (int dn = 0; dn < 4; ++dn) acc[p][dn] = f32x4{0.f, 0.f, 0.f, 0.f};
-        branch_reg2<F16, NT, VREG>(ft, Vt, ldv, a.S, bq, a.scale, 1.0f, acc, lane);
+        branch_reg2<F16, NT>(ft, Vt, ldv, a.S, bq, a.scale, 1.0f, acc, lane);
         if (NT_IP > 0)
-            branch_reg2<F16, (NT_IP > 0 ? NT_IP : 1), VREG>(reinterpret_cast<const kv_frag<(NT_IP > 0 ? NT_IP : 1)>&>(fi), Vip, ldv_ip, a.S_ip, bq, a.scale,
+            branch_reg2<F16, (NT_IP > 0 ? NT_IP : 1)>(reinterpret_cast<const kv_frag<(NT_IP > 0 ? NT_IP : 1)>&>(fi), Vip, ldv_ip, a.S_ip, bq, a.scale,
                                                             a.ip_scale, acc, lane);
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
@@ -389,18 +375,11 @@ extern "C" int eegclip_cross_attn_fwd(const void* q, const void* k, const void* 
     const int ldv = ca_ldv(nt), ldv_ip = ca_ldv(nt_ip);
     const size_t lds = sizeof(unsigned short) * ((size_t)nt * 16 * CA_KLD + CA_D * ldv + (size_t)nt_ip * 16 * CA_KLD + (nt_ip ? CA_D * ldv_ip : 0));
     const dim3 grid((HW + CA_QB - 1) / CA_QB, heads, B);
-    const bool allow_reg = true;
-    if (allow_reg && nt == 5 && nt_ip <= 1) {            // SDXL: 77 text tokens, 0 / 4 image tokens -- K (and optionally V^T) fragments in registers
-        const bool vreg = false;                              // (V^T fragments in registers as well: measured slower)
+    if (nt == 5 && nt_ip <= 1) {            // SDXL: 77 text tokens, 0 / 4 image tokens -- K fragments in registers
         const bool f16 = dtype == EEGCLIP_DT_F16;
-#define EEG_CA_GO(F, I, V) EEG_LAUNCH((cross_attn_reg_kernel<F, 5, I, V>), grid, dim3(256), lds, stream, a)
-        if (vreg) {
-            if (nt_ip == 1) { if (f16) EEG_CA_GO(true, 1, true); else EEG_CA_GO(false, 1, true); }
-            else            { if (f16) EEG_CA_GO(true, 0, true); else EEG_CA_GO(false, 0, true); }
-        } else {
-            if (nt_ip == 1) { if (f16) EEG_CA_GO(true, 1, false); else EEG_CA_GO(false, 1, false); }
-            else            { if (f16) EEG_CA_GO(true, 0, false); else EEG_CA_GO(false, 0, false); }
-        }
+#define EEG_CA_GO(F, I) EEG_LAUNCH((cross_attn_reg_kernel<F, 5, I>), grid, dim3(256), lds, stream, a)
+        if (nt_ip == 1) { if (f16) EEG_CA_GO(true, 1); else EEG_CA_GO(false, 1); }
+        else            { if (f16) EEG_CA_GO(true, 0); else EEG_CA_GO(false, 0); }
 #undef EEG_CA_GO
         return (int)hipGetLastError();
     }

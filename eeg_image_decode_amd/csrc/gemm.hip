@@ -482,9 +482,8 @@ static bool same_shared(const eegclip_gemm_desc& a, const eegclip_gemm_desc& b) 
 }
 
 static int launch_gemm_grouped(const eegclip_gemm_desc* ds, int n, void* stream) {
-    const bool allow = true;
     bool akc = false, bkc = false, cpl = false;
-    int cls = (allow && n >= 2 && n <= GEMM_MAX_GROUPS) ? fast_class(ds[0], akc, bkc, cpl) : 0;
+    int cls = (n >= 2 && n <= GEMM_MAX_GROUPS) ? fast_class(ds[0], akc, bkc, cpl) : 0;
     gemm_group_table tb;
     tb.n = 0;
     tb.first[0] = 0;
@@ -527,9 +526,8 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 // ws_query: do not launch; report the split-K workspace the launch would use (0 unless it is routed to the BF16X3 kernels)
 static int launch_gemm(const eegclip_gemm_desc& d, void* stream, long long* ws_query) {
     if (ws_query) *ws_query = 0;
-    const bool allow_skinny = true;
     // skinny: few rows against k-contiguous operands, every map a plain stride, 16-byte loads legal, K long enough for the 16-way split
-    if (allow_skinny && d.M <= 32 && d.split_k == 1 && d.K >= 64 && (d.K & 3) == 0 && is_plain(d.Am) && is_plain(d.Ak) && is_plain(d.Bk) &&
+    if (d.M <= 32 && d.split_k == 1 && d.K >= 64 && (d.K & 3) == 0 && is_plain(d.Am) && is_plain(d.Ak) && is_plain(d.Bk) &&
         is_plain(d.Bn) && is_plain(d.Cm) && is_plain(d.Cn) && (!d.R || (is_plain(d.Rm) && is_plain(d.Rn))) && d.Ak.si == 1 && d.Bk.si == 1 &&
         d.Am.si >= 0 && d.Bn.si >= 0 && (d.Am.si & 3) == 0 && (d.Bn.si & 3) == 0 && aligned16(d.A) && aligned16(d.B)) {
         if (ws_query) return 0;
@@ -543,11 +541,10 @@ static int launch_gemm(const eegclip_gemm_desc& d, void* stream, long long* ws_q
     const bool ab_plain = is_plain(d.Am) && is_plain(d.Ak) && is_plain(d.Bk) && is_plain(d.Bn);
     const bool c_plain = is_plain(d.Cm) && is_plain(d.Cn) && (!d.R || (is_plain(d.Rm) && is_plain(d.Rn)));
     const bool plain = ab_plain && c_plain;
-    const bool allow_fast = true;
     bool akc = false, bkc = false;
     const int ntiles = gx * gy, chunk = (ntiles + 7) / 8;
     const dim3 fgrid(d.split_k == 1 ? 8 * chunk : 8 * ((d.split_k + 7) / 8) * ntiles);
-    if (allow_fast && ab_plain && d.K >= 2 && (long long)gx * gy < (1LL << 28) && fast_operand_ok(d.A, d.Am.si, d.Ak.si, d.M, d.K, akc) &&
+    if (ab_plain && d.K >= 2 && (long long)gx * gy < (1LL << 28) && fast_operand_ok(d.A, d.Am.si, d.Ak.si, d.M, d.K, akc) &&
         fast_operand_ok(d.B, d.Bn.si, d.Bk.si, d.N, d.K, bkc)) {
         if (ws_query) {
             if ((d.precision & 0xff) == EEGCLIP_PREC_BF16X3) *ws_query = gemm_x3_workspace_bytes(d);
@@ -568,7 +565,7 @@ static int launch_gemm(const eegclip_gemm_desc& d, void* stream, long long* ws_q
         return (int)hipGetLastError();
     }
     // both operands row-contiguous with k running through two-level maps (plain row maps, plain C): the K2 instantiation
-    if (allow_fast && c_plain && is_plain(d.Am) && is_plain(d.Bn) && d.Am.si == 1 && d.Bn.si == 1 && d.K >= 2 && (long long)gx * gy < (1LL << 28) &&
+    if (c_plain && is_plain(d.Am) && is_plain(d.Bn) && d.Am.si == 1 && d.Bn.si == 1 && d.K >= 2 && (long long)gx * gy < (1LL << 28) &&
         fast_k2_ok(d.A, d.Ak, d.M, d.K) && fast_k2_ok(d.B, d.Bk, d.N, d.K)) {
         if (ws_query) {
             if ((d.precision & 0xff) == EEGCLIP_PREC_BF16X3) *ws_query = gemm_x3_workspace_bytes(d);

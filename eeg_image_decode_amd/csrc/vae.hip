@@ -46,17 +46,17 @@ struct cv_args {
 // EXT: the UNet's form (csrc/unet.hip's layers around it; diffusers 0.30.0 UNet2DConditionModel) -- Cout % 64 == 0 with the last 128-wide N tile masked (weight
 // rows >= Cout are never read: those DMA lanes fetch row Cout - 1, whose columns nobody stores) and the per-image channel bias `cb` in the epilogue (ResnetBlock2D's
 // time-embedding add, folded into conv1).  EXT = false is the VAE's form, unchanged.
-// SPEC (round 6): four extra PRODUCER waves issue every LDS-DMA instruction (and do the address arithmetic in front of it); the four MFMA waves only read
+// Four extra PRODUCER waves (round 6) issue every LDS-DMA instruction (and do the address arithmetic in front of it); the four MFMA waves only read
 // fragments and feed the matrix pipe, and meet the producers at the one barrier per k-tile -- a wave that does both is in order and stalls in every DMA issue
 // with its MFMAs unissued behind it (csrc/infonce_fused.hip, NPRD).
-template <bool F16, bool SPEC, bool EXT>
-__global__ __launch_bounds__(SPEC ? 512 : 256) void conv16_kernel(const cv_args a) {
+template <bool F16, bool EXT>
+__global__ __launch_bounds__(512) void conv16_kernel(const cv_args a) {
     EEG_LDS_BASE(unsigned char, lds);
     const int logical = (int)(blockIdx.x & 7) * a.chunk + (int)(blockIdx.x >> 3);
     if (logical >= a.ntiles) return;
     const int m0 = (logical / a.tiles_n) * CV_T, n0 = (logical % a.tiles_n) * CV_T;
     const int t = threadIdx.x, lane = t & 63, wave_ = wave_uniform(t >> 6);
-    const bool producer = SPEC && wave_ >= 4;                 // (wave-uniform)
+    const bool producer = wave_ >= 4;                         // (wave-uniform)
     const int wave = wave_ & 3;                               // index among the MFMA waves / among the DMA waves
     const int wm = wave >> 1, wn = wave & 1;
     const int r32 = lane & 31, h = lane >> 5;
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(SPEC ? 512 : 256) void conv16_kernel(const cv_args 
             fon[s][i] = CV_TILE_B + rn * CV_ROWB + (((2 * s + h) ^ swz(rn)) & 7) * 16;
         }
     const int ktiles = a.KS * a.KS * cpt;
-    if (!SPEC || producer) {
+    if (producer) {
 #pragma unroll
         for (int p = 0; p < CV_NS - 1; ++p)
             if (p < ktiles) {
@@ -134,8 +134,6 @@ __global__ __launch_bounds__(SPEC ? 512 : 256) void conv16_kernel(const cv_args 
                 for (int dnum = 0; dnum < 8; ++dnum) issue_one(p, dnum);
                 advance();
             }
-    }
-    if (producer) {
         for (int kt = 0; kt < ktiles; ++kt) {
             const int newer = ktiles - 1 - kt < CV_NS - 2 ? ktiles - 1 - kt : CV_NS - 2;
             if (newer >= 2) wait_vmcnt<16>();
@@ -151,14 +149,7 @@ __global__ __launch_bounds__(SPEC ? 512 : 256) void conv16_kernel(const cv_args 
         return;                                               // (the epilogue has no barrier)
     }
     for (int kt = 0; kt < ktiles; ++kt) {
-        if (!SPEC) {
-            const int newer = ktiles - 1 - kt < CV_NS - 2 ? ktiles - 1 - kt : CV_NS - 2;
-            if (newer >= 2) wait_vmcnt<16>();
-            else if (newer == 1) wait_vmcnt<8>();
-            else wait_vmcnt<0>();
-        }
         raw_barrier();
-        const bool refill = !SPEC && kt + CV_NS - 1 < ktiles;
         const unsigned char* st = lds + (kt % CV_NS) * CV_STAGE_B;
         bf16x8 am[2][2], wf[2][2];
         // (what a step's first MFMA takes is read last and the next step's reads go out behind that MFMA: csrc/infonce_fused.hip, round 6)
@@ -179,17 +170,14 @@ __global__ __launch_bounds__(SPEC ? 512 : 256) void conv16_kernel(const cv_args 
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     acc[j][i] = mma32<F16>(wf[set][j], am[set][i], acc[j][i]);
-                    const int mi = 4 * s + 2 * j + i;
                     if (j == 0 && i == 0 && s + 1 < 4) {
                         sched_fence();
                         read_step(s + 1, (s + 1) & 1);
                         sched_fence();
                     }
-                    if (refill && (mi & 1)) issue_one(kt + CV_NS - 1, mi >> 1);
                 }
             sched_fence();
         }
-        if (refill) advance();
     }
     // ---- epilogue: lane (r32, h) owns pixel m = m0 + 64 wm + 32 i + r32; registers 4 eq .. 4 eq + 3 of n tile j are channels n0 + 64 wn + 32 j + 8 eq + 4 h ..
 #pragma unroll
@@ -529,16 +517,10 @@ extern "C" int eegclip_conv16(const eegclip_conv16_desc* d, void* stream) {
         a.ntiles = a.tiles_n * ((a.M + CV_T - 1) / CV_T);
         a.chunk = (a.ntiles + 7) / 8;
         const size_t lds = (size_t)CV_NS * CV_STAGE_B;
-        static const bool spec = [] { const char* e = getenv("EEGCLIP_CONV16_PRODUCERS"); return !(e && e[0] == '0'); }();      // (A/B aid)
-        const dim3 grid((unsigned)(8 * a.chunk)), block(spec ? 512 : 256);
-#define EEG_CV(F, S, X) EEG_LAUNCH((conv16_kernel<F, S, X>), grid, block, lds, stream, a)
-        if (ext) {
-            if (spec) { if (f16) EEG_CV(true, true, true); else EEG_CV(false, true, true); }
-            else      { if (f16) EEG_CV(true, false, true); else EEG_CV(false, false, true); }
-        } else {
-            if (spec) { if (f16) EEG_CV(true, true, false); else EEG_CV(false, true, false); }
-            else      { if (f16) EEG_CV(true, false, false); else EEG_CV(false, false, false); }
-        }
+        const dim3 grid((unsigned)(8 * a.chunk)), block(512);       // 4 MFMA + 4 producer (DMA) waves
+#define EEG_CV(F, X) EEG_LAUNCH((conv16_kernel<F, X>), grid, block, lds, stream, a)
+        if (ext) { if (f16) EEG_CV(true, true); else EEG_CV(false, true); }
+        else     { if (f16) EEG_CV(true, false); else EEG_CV(false, false); }
 #undef EEG_CV
         return (int)hipGetLastError();
     }

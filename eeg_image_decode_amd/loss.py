@@ -76,8 +76,8 @@ MAX_BLOCKS_PER_LAUNCH = 8          # IF_MAX_PROB of csrc/infonce_fused.hip (eegc
 
 def head_gemm_enabled(n, K, Dm):
     """the query gradient dA = [G_1 | .. | G_T] [B_1; ..; B_T] on the K-parallel plane GEMM (csrc/head_gemm.hip, round 6): gradient matrices as planes
-    straight from the InfoNCE gradient pass, the stacked target planes read k-major (no transposed copy); EEGCLIP_HEAD_GEMM=0 pins the fp32-operand GEMM"""
-    return os.environ.get("EEGCLIP_HEAD_GEMM", "1") != "0" and n % 4 == 0 and K % 32 == 0 and Dm % 8 == 0
+    straight from the InfoNCE gradient pass, the stacked target planes read k-major (no transposed copy); other shapes keep the fp32-operand GEMM"""
+    return n % 4 == 0 and K % 32 == 0 and Dm % 8 == 0
 
 
 def stacked_target_planes(a_, bs, planes):
@@ -113,8 +113,8 @@ def query_grad_slabs(Gp, tp, n, K, Dm, slabs=None):
 
 def infonce_small_enabled(n, T_, planes):
     """one process at the training batch size: logits as ONE K-parallel plane GEMM + two row-block kernels (csrc/infonce_small.hip, round 6) instead of the
-    tile kernels' 64 workgroups that each walk D alone; EEGCLIP_INFONCE_SMALL=0 pins the tile kernels"""
-    return planes == 2 and os.environ.get("EEGCLIP_INFONCE_SMALL", "1") != "0" and bool(lib().eegclip_infonce_small_supported(int(n), int(T_)))
+    tile kernels' 64 workgroups that each walk D alone"""
+    return planes == 2 and bool(lib().eegclip_infonce_small_supported(int(n), int(T_)))
 
 
 def infonce_small(aq, tp, n, T_, Dm, weights, sc, acc, Gp):
@@ -175,7 +175,7 @@ def fused_infonce(blocks, n, N, Dm, planes, n_total, sc, acc, want_grad, G_out=N
     # gradient pass forms the log-sum-exps itself -- no finalize launch between the two tile launches (eegclip_infonce_fused_grad_finalize)
     covered = sorted(i for pair in want_grad for i in pair if i is not None)
     inline = (n == N and bool(want_grad) and covered == list(range(nb)) and all(ki is not None for _, ki in want_grad)
-              and all(blocks[bi][3] == blocks[ki][3] for bi, ki in want_grad) and os.environ.get("EEGCLIP_INFONCE_INLINE_FINALIZE", "1") != "0")
+              and all(blocks[bi][3] == blocks[ki][3] for bi, ki in want_grad))
     for c0 in range(0, nb, MAX_BLOCKS_PER_LAUNCH):                  # (any number of targets: the launch table holds 8 blocks)
         chunk = (_abi.InfonceProblem * min(MAX_BLOCKS_PER_LAUNCH, nb - c0))(*arr[c0:c0 + MAX_BLOCKS_PER_LAUNCH])
         check(L.eegclip_infonce_fused_fwd(chunk, len(chunk), n, N, Dm, planes, n_total, sc.data_ptr(), None if inline else acc.data_ptr(), st),
@@ -354,8 +354,7 @@ def sharded_blocks(local_loss, gather_with_grad, rank, W, a_, bs, a_all, b_alls,
     da, ga = None, None
     dbs, gbs = [None] * len(bs), [None] * len(bs)
     fused = fused_enabled(n, N, Dm) and all(b.shape == a_.shape for b in bs)
-    if (fused and local_loss and gather_with_grad and need and need_a and not any(need_b) and len(bs) <= 8 and head_gemm_enabled(n, len(bs) * N, Dm)
-            and os.environ.get("EEGCLIP_SHARDED_PLANES", "1") != "0"):
+    if (fused and local_loss and gather_with_grad and need and need_a and not any(need_b) and len(bs) <= 8 and head_gemm_enabled(n, len(bs) * N, Dm)):
         da, ga = _sharded_blocks_on_planes(rank, W, a_, bs, a_all, b_alls, weights, sc, acc, planes)
         return da, ga, dbs, gbs
     if fused:

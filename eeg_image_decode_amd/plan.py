@@ -20,11 +20,6 @@ from ._lib import check, cuda_available, current_stream, lib, use_stream
 D = _abi.dim
 
 
-# split-K through per-slice slabs + an ordered reduction instead of atomics on C: run-to-run bit-reproducible weight gradients.  Measured equal in
-# time at the step's split (256 x 250 x 16384 / 32 slices: 31.4 us atomics, 32.3 us slabs; tools/wgrad_probe.py), so it is opt-in.
-_SPLITK_WORKSPACE = False
-
-
 _SIDE_PRIORITY = 0                                                    # HIP stream priority of a plan's second stream (range on this stack: 0 .. -1; round 5: -1 = 1.8 ms per step instead of 0.75)
 
 
@@ -62,7 +57,7 @@ class Plan:
         self.skip = ()         # op indices left out of the next run()s (e.g. the value-embedding GEMMs of subjects absent from the batch)
         self._c = None         # compiled form for the C executor (eegclip_plan_run): built on the first untimed run
         self._c_skip = ()
-        self.use_c_executor = os.environ.get("EEGCLIP_PLAN_EXEC", "c") != "python"
+        self.use_c_executor = True      # (False: the Python executor below -- timed runs always take it; tools set it for host-time comparisons)
 
     # -- generic positional op; `seed_at` = index of the seed argument (patched at run time)
     def call(self, fname, *args, seed_at=None, side=False):
@@ -91,15 +86,6 @@ class Plan:
 
     def gemm(self, *a, side=False, **k):
         d = self.desc(*a, **k)
-        if d.split_k > 1 and _SPLITK_WORKSPACE:
-            # split-K through a scratch buffer of this op's own (ops of one plan may overlap on its two streams): partial tiles + one ordered
-            # reduction instead of split_k atomic adds per output element
-            nbytes = int(self.L.eegclip_gemm_workspace_bytes(ctypes.byref(d)))
-            if nbytes > 0:
-                import torch
-                ws = torch.zeros(nbytes // 4, dtype=torch.float32, device="cuda" if torch.cuda.is_available() else "cpu")   # (cpu: the test emulator)
-                self._keep.append(ws)
-                d.workspace, d.workspace_bytes = ws.data_ptr(), nbytes
         if d.drop_p > 0.0:
             self._seed_descs.append(d)
         self.ops.append((self.L.eegclip_gemm_f32, [ctypes.byref(d), None], "eegclip_gemm_f32", side))

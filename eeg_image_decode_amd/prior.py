@@ -450,7 +450,7 @@ class _PriorEngine:
         E, Td, Cd, h0, W = m.embed_dim, m.time_embed_dim, m.cond_dim, m.hidden_dim[0], self.wide
 
         def wgrad(problems):
-            """weight (+ bias) gradients on the plan's second stream: (weight key, bias key, dY planes, ld, M, X planes, ld, N); small outputs are
+            """weight (+ bias) gradients in one launch: (weight key, bias key, dY planes, ld, M, X planes, ld, N); small outputs are
             K-sliced (fp32 atomics onto few addresses), large ones are one read-modify-write pass"""
             arr = (_abi.WgradPlanesProblem * len(problems))()
             for i, (wk, bk, dy, lda, M, x, ldb, Nn) in enumerate(problems):
@@ -459,17 +459,14 @@ class _PriorEngine:
                 arr[i] = _abi.WgradPlanesProblem(a_hi=dy[0], a_lo=dy[1], lda=lda, b_hi=x[0], b_lo=x[1], ldb=ldb, rows=N, M=M, N=Nn, out=_p(G[wk]), ldo=Nn,
                                                  bias_out=_p(G[bk]), slices=slices)
             pl._keep.append(arr)
-            pl.call("eegclip_wgrad_planes", arr, len(problems), side=not merge)
+            pl.call("eegclip_wgrad_planes", arr, len(problems))
 
-        # EEGCLIP_PRIOR_WGRAD_MERGE (default 1): the 22 weight gradients wait for the end of the dX chain and run as two launches of <= 12 problems instead
+        # the 22 weight gradients wait for the end of the dX chain and run merged on the main stream instead
         # of eleven launches "beside" the chain -- a weight-gradient workgroup (128 KB of LDS) and a plane-GEMM workgroup (64 KB x 2) exclude each other on
         # a CU, so the second stream did not overlap, it queued (main 0.70 ms + second stream 0.33 ms = the 1.03 ms span of the trace).  Every operand
         # (per-stage dY / X planes) is still intact at the end of the backward.
-        merge = os.environ.get("EEGCLIP_PRIOR_WGRAD_MERGE", "1") != "0"
         pending = []
-        if merge:
-            wgrad_now = wgrad
-            wgrad = lambda problems: pending.extend(problems)       # noqa: E731
+        wgrad_now, wgrad = wgrad, pending.extend
 
         n_st, n_enc = len(self.stages), m.num_layers - 1
         pl.call("eegclip_split_bf16", _p(b["dout"]), b["doutP"][0].data_ptr(), b["doutP"][1].data_ptr(), N * E)
@@ -508,10 +505,9 @@ class _PriorEngine:
         wgrad([(s0["t"] + "linear_1.weight", s0["t"] + "linear_1.bias", self._pl(b["DT1P"]), W, W, self._pl(b["tembp"]), Td, Td),
                ("input_layer.0.weight", "input_layer.0.bias", di, h0, h0, self._pl(b["xp"]), E, E)])
         # (eegclip_wgrad_planes: <= 24 problems per launch -- ONE launch since round 6: two launches of 360 + 444 workgroups were 2 + 2 rounds on 256 CUs,
-        #  804 workgroups are 3.1; EEGCLIP_PRIOR_WGRAD_CHUNK=12: the two launches, A/B aid)
-        chunk = int(os.environ.get("EEGCLIP_PRIOR_WGRAD_CHUNK", "24"))
-        for i in range(0, len(pending), chunk):
-            wgrad_now(pending[i:i + chunk])
+        #  804 workgroups are 3.1)
+        for i in range(0, len(pending), 24):
+            wgrad_now(pending[i:i + 24])
         return pl
 
     def forward(self, x, t, c, p, cond_rows=None):

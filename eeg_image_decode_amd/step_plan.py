@@ -130,39 +130,18 @@ class StepPlan:
         self.split_op = None
         if not self.on_planes:
             self.split_op = len(pl.ops)
-            pl.ops.append((L.eegclip_split_rows, [None, T_, None], "eegclip_split_rows", os.environ.get("EEGCLIP_START_SIDE", "1") != "0"))
+            pl.ops.append((L.eegclip_split_rows, [None, T_, None], "eegclip_split_rows", True))
         # ---- encoder forward
         f0 = splice(self.fwd)
         self.fwd_base = f0
         self.out_op = f0 + self.fwd.out_op
-        # ---- running train accuracy: raw z @ class_feats^T, top-1, count: second stream.  The ops are emitted INSIDE the backward, right behind its first
-        # second-stream launch (the head LayerNorm's parameter gradients), so that they share that fork instead of paying one of their own
+        # ---- running train accuracy: raw z @ class_feats^T, top-1, count: second stream, from planes on csrc/head_gemm.hip (a step plan exists only in the
+        # split-bf16 arithmetic -- the fused transformer block is required above -- where the head always leaves its output as planes): the class table is
+        # split ONCE per table (run()); the fp32-operand GEMM took 30 us alone and 90 us beside the conv stack's backward
         sc_ptr = model.logit_scale.detach().reshape(1).data_ptr()
         ncp = (n_classes + 3) // 4 * 4
-        self.acc_on_planes = bool(getattr(self.fwd, "head_planes", False)) and os.environ.get("EEGCLIP_HEAD_GEMM", "1") != "0"
-        if self.acc_on_planes:
-            # (round 6) from planes on csrc/head_gemm.hip: the query features leave the head's LayerNorm as planes anyway, the class table is split ONCE per
-            # table (run()); the fp32-operand GEMM took 30 us alone and 90 us beside the conv stack's backward
-            self.logits = torch.empty(B, ncp, dtype=torch.float32, device=dev)
-            self.class_planes = torch.zeros(2, ncp, Dm, dtype=torch.bfloat16, device=dev)       # (rows >= n_classes: zero padding up to a multiple of 4 columns)
-            self.acc_desc = None
-        else:
-            self.logits = torch.empty(B, n_classes, dtype=torch.float32, device=dev)
-            self.acc_desc = _abi.GemmDesc(M=B, N=n_classes, K=Dm, A=0, Am=D(Dm), Ak=D(1), B=0, Bk=D(1), Bn=D(Dm), C=self.logits.data_ptr(), Cm=D(n_classes), Cn=D(1),
-                                          Cpre=None, bias_n=None, bias_m=None, R=None, Rm=D(0), Rn=D(0), alpha=1.0, accumulate=0, act=0, drop_p=0.0, seed=0,
-                                          drop_site=0, split_k=1, precision=self.fwd.precision)
-            pl._keep.append(self.acc_desc)
-
-        def accuracy_ops():
-            if self.acc_on_planes:
-                pl.call_desc("eegclip_head_gemm", _abi.HeadGemmDesc(a_hi=self.q_planes[0].data_ptr(), a_lo=self.q_planes[1].data_ptr(), b_hi=self.class_planes[0].data_ptr(),
-                                                                   b_lo=self.class_planes[1].data_ptr(), lda=Dm, ldb=Dm, M=B, N=ncp, K=Dm, slices=1, slab_stride=0,
-                                                                   C=self.logits.data_ptr(), ldc=ncp), side=True)
-            else:
-                pl.ops.append((L.eegclip_gemm_f32, [ctypes.byref(self.acc_desc), None], "eegclip_gemm_f32", True))
-            self.count_op = len(pl.ops)
-            pl.call("eegclip_top1_count", self.logits.data_ptr(), B, n_classes, self.logits.shape[1], sc_ptr, 0, 0, side=True)
-
+        self.logits = torch.empty(B, ncp, dtype=torch.float32, device=dev)
+        self.class_planes = torch.zeros(2, ncp, Dm, dtype=torch.bfloat16, device=dev)       # (rows >= n_classes: zero padding up to a multiple of 4 columns)
         self.q_planes = torch.empty(2, B, Dm, dtype=torch.bfloat16, device=dev)                 # the query features, written by the head's LayerNorm
         # ---- image + text InfoNCE on the fused kernels (loss.py: _ClipLossFn.forward, the W == 1 fused branch).  Operand planes: the targets are inputs of the
         # step -- split (and, for the query gradient, split TRANSPOSED: round 6) by second-stream launches at the very start; the query features leave the
@@ -186,13 +165,9 @@ class StepPlan:
                                                         ld_src=Dm, ld_out=Dm, transpose=0, copy=self.stack[i * B].data_ptr() if self.stack is not None else None,
                                                         ld_copy=Dm)
         fn, args, name, side = pl.ops[self.out_op]
-        if name == "eegclip_residual_layernorm_fwd_slabs":              # (round 6: the head's LayerNorm adds the second Linear's slabs; planes are arguments 19 / 20)
-            args[19], args[20] = self.q_planes[0].data_ptr(), self.q_planes[1].data_ptr()
-        else:
-            if name != "eegclip_residual_layernorm_fwd":
-                raise NotApplicable(f"unexpected output op {name}")
-            pl.ops[self.out_op] = (L.eegclip_residual_layernorm_fwd_planes, args[:-1] + [self.q_planes[0].data_ptr(), self.q_planes[1].data_ptr(), None],
-                                   "eegclip_residual_layernorm_fwd_planes", side)
+        if name != "eegclip_residual_layernorm_fwd_slabs":
+            raise NotApplicable(f"unexpected output op {name}")
+        args[19], args[20] = self.q_planes[0].data_ptr(), self.q_planes[1].data_ptr()      # (the head's LayerNorm adds the second Linear's slabs; planes are arguments 19 / 20)
         ws = int(L.eegclip_infonce_fused_workspace_floats(B, B))
         self.if_buf = torch.empty(2 * T_ * (ws + 2 * B), dtype=torch.float32, device=dev)
         if self.on_planes:
@@ -231,10 +206,12 @@ class StepPlan:
             pl.join()
         # (round 6) the accuracy readout forks HERE, right behind the forward: its ~30 us of second-stream work overlap the loss and the head's backward -- small
         # launches that leave most of the chip idle -- instead of queueing behind the conv stack's backward, whose workgroups own the CUs' LDS (the plane
-        # GEMM took 83 us there).  EEGCLIP_ACC_EARLY=0: inside the backward's first fork (round 5's place; A/B aid)
-        self.acc_early = os.environ.get("EEGCLIP_ACC_EARLY", "1") != "0" and self.acc_on_planes
-        if self.acc_early:
-            accuracy_ops()
+        # GEMM took 83 us there)
+        pl.call_desc("eegclip_head_gemm", _abi.HeadGemmDesc(a_hi=self.q_planes[0].data_ptr(), a_lo=self.q_planes[1].data_ptr(), b_hi=self.class_planes[0].data_ptr(),
+                                                           b_lo=self.class_planes[1].data_ptr(), lda=Dm, ldb=Dm, M=B, N=ncp, K=Dm, slices=1, slab_stride=0,
+                                                           C=self.logits.data_ptr(), ldc=ncp), side=True)
+        self.count_op = len(pl.ops)
+        pl.call("eegclip_top1_count", self.logits.data_ptr(), B, n_classes, ncp, sc_ptr, 0, 0, side=True)
         self.small = self.on_planes and eloss.infonce_small_enabled(B, T_, self.planes)
         if self.small:
             # (round 6) one process at the training batch size: the raw logits of all targets as ONE K-parallel plane GEMM, then two row-block kernels
@@ -252,16 +229,10 @@ class StepPlan:
             pl.call("eegclip_infonce_small_grad", B, T_, sc_ptr, self.s_ws.data_ptr(), *w4, self.Gp[0].data_ptr(), self.Gp[1].data_ptr(), NC, 0,
                     eng.G["logit_scale"].data_ptr())                        # d loss / d scale straight into its gradient
         # (loss.fused_infonce's training form: the forward leaves the per-tile partials, the gradient pass finalises them itself and adds the loss)
-        elif os.environ.get("EEGCLIP_INFONCE_INLINE_FINALIZE", "1") != "0":
+        else:
             pl.call("eegclip_infonce_fused_fwd", arr, 2 * T_, B, B, Dm, self.planes, B, sc_ptr, None)
             self.if_fwd_op, self.loss_arg = len(pl.ops), 8                  # (the op whose `loss` argument is patched per step)
             pl.call("eegclip_infonce_fused_grad_finalize", garr, T_, B, B, Dm, self.planes, B, sc_ptr, 0, eng.G["logit_scale"].data_ptr())      # d loss / d scale straight into its gradient
-        else:
-            for t_ in range(T_):
-                garr[t_].part_k = garr[t_].diag_k = None
-            self.if_fwd_op, self.loss_arg = len(pl.ops), 8
-            pl.call("eegclip_infonce_fused_fwd", arr, 2 * T_, B, B, Dm, self.planes, B, sc_ptr, 0)
-            pl.call("eegclip_infonce_fused_grad", garr, T_, B, B, Dm, self.planes, B, sc_ptr, eng.G["logit_scale"].data_ptr())
         # dA = [G_img | G_txt] [img; txt]: one launch, K = T B
         self.mse_op = None
         if self.on_planes:
@@ -284,12 +255,11 @@ class StepPlan:
                               seed=0, drop_site=0, split_k=1, precision=_abi.PREC_BF16X3)
             pl._keep.append(d)
             pl.ops.append((L.eegclip_gemm_f32, [ctypes.byref(d), None], "eegclip_gemm_f32", False))
-        # ---- encoder backward, op by op (self.bwd_index: backward-plan op -> this plan's op).  Inserted on the way: the accuracy readout behind the backward's
-        # first second-stream launch (unless it forked behind the forward), and -- round 6 -- the optimizer update of the EARLY gradient bucket (loss scale,
+        # ---- encoder backward, op by op (self.bwd_index: backward-plan op -> this plan's op).  Inserted on the way: the optimizer update of the EARLY gradient bucket (loss scale,
         # conv stack, projection head: 82 % of the parameters) on the second stream as soon as the conv stack's backward has issued its last gradient, under
         # the transformer block's backward; the update at the end of the step then covers only the block's parameters (17 -> ~5 us on the exposed tail)
         self._plan_adamw(optimizer, eng)
-        early_cut = getattr(self.bwd, "early_cut", None) if (self.adam_early and os.environ.get("EEGCLIP_ADAMW_EARLY", "1") != "0") else None
+        early_cut = getattr(self.bwd, "early_cut", None) if self.adam_early else None
         taps_op = getattr(self.bwd, "taps_op", None)
         if early_cut is None or (taps_op is not None and taps_op < early_cut):
             early_cut = None
@@ -314,8 +284,6 @@ class StepPlan:
             if (early_cut is not None and i == taps_op) or i == fuse_op:
                 continue                                     # (moved in front of the early update / behind the join, into the optimizer launch)
             emit_bwd(i)
-            if i == self.bwd.dout_par_op and not self.acc_early:
-                accuracy_ops()
             if early_cut is not None and i == early_cut - 1:
                 if taps_op is not None:
                     emit_bwd(taps_op)
@@ -356,25 +324,16 @@ class StepPlan:
         ncp = (n_classes + 3) // 4 * 4
         self.q_planes = torch.empty(2, B, Dm, dtype=torch.bfloat16, device=dev)
         fn, args, name, side = pl.ops[self.out_op]
-        self.acc_on_planes = name == "eegclip_residual_layernorm_fwd_slabs" and os.environ.get("EEGCLIP_HEAD_GEMM", "1") != "0"
-        if self.acc_on_planes:
-            args[19], args[20] = self.q_planes[0].data_ptr(), self.q_planes[1].data_ptr()
-            self.logits = torch.empty(B, ncp, dtype=torch.float32, device=dev)
-            self.class_planes = torch.zeros(2, ncp, Dm, dtype=torch.bfloat16, device=dev)
-            self.acc_desc = None
-            pl.call_desc("eegclip_head_gemm", _abi.HeadGemmDesc(a_hi=self.q_planes[0].data_ptr(), a_lo=self.q_planes[1].data_ptr(), b_hi=self.class_planes[0].data_ptr(),
-                                                               b_lo=self.class_planes[1].data_ptr(), lda=Dm, ldb=Dm, M=B, N=ncp, K=Dm, slices=1, slab_stride=0,
-                                                               C=self.logits.data_ptr(), ldc=ncp), side=True)
-        else:
-            self.logits = torch.empty(B, n_classes, dtype=torch.float32, device=dev)
-            self.acc_desc = _abi.GemmDesc(M=B, N=n_classes, K=Dm, A=0, Am=D(Dm), Ak=D(1), B=0, Bk=D(1), Bn=D(Dm), C=self.logits.data_ptr(), Cm=D(n_classes), Cn=D(1),
-                                          Cpre=None, bias_n=None, bias_m=None, R=None, Rm=D(0), Rn=D(0), alpha=1.0, accumulate=0, act=0, drop_p=0.0, seed=0,
-                                          drop_site=0, split_k=1, precision=self.fwd.precision)
-            pl._keep.append(self.acc_desc)
-            pl.ops.append((L.eegclip_gemm_f32, [ctypes.byref(self.acc_desc), None], "eegclip_gemm_f32", True))
+        if name != "eegclip_residual_layernorm_fwd_slabs":
+            raise NotApplicable(f"unexpected output op {name}")
+        args[19], args[20] = self.q_planes[0].data_ptr(), self.q_planes[1].data_ptr()
+        self.logits = torch.empty(B, ncp, dtype=torch.float32, device=dev)
+        self.class_planes = torch.zeros(2, ncp, Dm, dtype=torch.bfloat16, device=dev)
+        pl.call_desc("eegclip_head_gemm", _abi.HeadGemmDesc(a_hi=self.q_planes[0].data_ptr(), a_lo=self.q_planes[1].data_ptr(), b_hi=self.class_planes[0].data_ptr(),
+                                                           b_lo=self.class_planes[1].data_ptr(), lda=Dm, ldb=Dm, M=B, N=ncp, K=Dm, slices=1, slab_stride=0,
+                                                           C=self.logits.data_ptr(), ldc=ncp), side=True)
         self.count_op = len(pl.ops)
-        pl.call("eegclip_top1_count", self.logits.data_ptr(), B, n_classes, self.logits.shape[1], sc_ptr, 0, 0, side=True)
-        self.acc_early = True
+        pl.call("eegclip_top1_count", self.logits.data_ptr(), B, n_classes, ncp, sc_ptr, 0, 0, side=True)
         # ---- the loss between the collectives
         b0_holder = {}
 
@@ -546,20 +505,14 @@ class StepPlan:
         op = out.data_ptr()
         pl.set_arg(self.out_op, 8, op)
         cp = (class_feats.data_ptr(), class_feats._version)
-        if self.acc_on_planes:
-            if cp != self._class_ptr:                  # a new (or modified) class table: its planes, once
-                nc = class_feats.shape[0]
-                it = (_abi.SplitItem * 1)(_abi.SplitItem(src=class_feats.data_ptr(), hi=self.class_planes[0].data_ptr(), lo=self.class_planes[1].data_ptr(), rows=nc,
-                                                          cols=1024, ld_src=1024, ld_out=1024, transpose=0))
-                rc = lib().eegclip_split_rows(it, 1, raw_stream())
-                if rc:
-                    raise RuntimeError(f"eegclip_split_rows returned {rc}")
-                self._class_ptr = cp
-        else:
-            self.acc_desc.A = op
-            if cp != self._class_ptr:
-                self.acc_desc.B = cp[0]
-                self._class_ptr = cp
+        if cp != self._class_ptr:                  # a new (or modified) class table: its planes, once
+            nc = class_feats.shape[0]
+            it = (_abi.SplitItem * 1)(_abi.SplitItem(src=class_feats.data_ptr(), hi=self.class_planes[0].data_ptr(), lo=self.class_planes[1].data_ptr(), rows=nc,
+                                                      cols=1024, ld_src=1024, ld_out=1024, transpose=0))
+            rc = lib().eegclip_split_rows(it, 1, raw_stream())
+            if rc:
+                raise RuntimeError(f"eegclip_split_rows returned {rc}")
+            self._class_ptr = cp
         pl.set_arg(self.count_op, 5, labels.data_ptr())
         pl.set_arg(self.count_op, 6, correct.data_ptr())
         if self.world > 1:

@@ -72,9 +72,8 @@ def test_fused_token_block_equals_the_unfused_plan_on_the_gpu(B, train, subject,
     check_fused_forward_equals_the_unfused_plan("cuda", B, train, subject, monkeypatch)
 
 
-def _grads(dev, B, train, subject, fused, monkeypatch, variant=0):
+def _grads(dev, B, train, subject, fused, monkeypatch):
     monkeypatch.setenv("EEGCLIP_TOKEN_BLOCK", "1" if fused else "0")
-    monkeypatch.setenv("EEGCLIP_WGRAD_VARIANT", str(variant))
     m = _model(dev)
     m.train(train)
     x = torch.from_numpy(syn.eeg_batch(SEED + 32, B)).to(dev)
@@ -124,10 +123,11 @@ def test_fused_token_block_backward_equals_the_unfused_plan_on_the_gpu(B, train,
 
 
 def check_both_workgroup_shapes_of_the_weight_gradient_kernel(dev, B, monkeypatch):
-    """EEGCLIP_WGRAD_VARIANT=1 (256-thread workgroups of csrc/wgrad_tok.hip) in the plan against the default (bit-identity of the two kernel shapes on the
-    same operands is tests/test_kernels_wgrad.py; here the operands carry the run-to-run round-off of the atomics upstream)"""
+    """two builds of the default plan (fresh model and engine each, same seeds) agree within the run-to-run round-off of the atomics upstream of the
+    weight gradients.  The plan launches one workgroup shape of csrc/wgrad_tok.hip (512 threads); the two shapes themselves are compared, bit for bit on
+    the same operands, in tests/test_kernels_wgrad.py"""
     g0, _ = _grads(dev, B, True, 1, True, monkeypatch)
-    g1, _ = _grads(dev, B, True, 1, True, monkeypatch, variant=1)
+    g1, _ = _grads(dev, B, True, 1, True, monkeypatch)
     assert g0.keys() == g1.keys()
     for k, r in g0.items():
         if not k.endswith("key_projection.bias"):
