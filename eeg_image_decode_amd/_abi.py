@@ -159,7 +159,7 @@ class PlanOp(C.Structure):
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_GRAD = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3 = 0, 1
-ABI_VERSION = 22
+ABI_VERSION = 23
 DT_BF16, DT_F16, DT_F32 = 0, 1, 2
 SRC_U8_HWC, RESIZE_BILINEAR, RESIZE_BICUBIC = 3, 2, 3
 SSIM_TILE_H, SSIM_TILE_W = 32, 32
@@ -325,6 +325,9 @@ PROTOTYPES = {
     "eegclip_cstack_bwd_taps_reduce": [_P, _I, _P, _P],
     "eegclip_cstack_bwd_w2_workspace_floats": [_I, _I],
     "eegclip_cstack_bwd_w2": [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "eegclip_cstack_bwd_rows_count": [_I, _I],
+    "eegclip_cstack_bwd_stats_w2": [C.POINTER(CstackBwdDesc), _P, _P],
+    "eegclip_cstack_w2_reduce": [_P, _I, _I, _P, _P],
     "eegclip_pixcorr_ssim_workspace_bytes": [_I, _I, _I],
     "eegclip_pixcorr_ssim": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     "eegclip_two_way_workspace_bytes": [_I, _I],
@@ -345,7 +348,7 @@ PROTOTYPES = {
     "eegclip_time_next_launch": [_P, _P],
     "eegclip_timing_elapsed_ms": [_P, _P],
 }
-RESTYPES = {"eegclip_timing_event_create": C.c_void_p, "eegclip_timing_elapsed_ms": C.c_float}
+RESTYPES = {"eegclip_timing_event_create": C.c_void_p, "eegclip_timing_elapsed_ms": C.c_float, "eegclip_cstack_bwd_rows_count": C.c_longlong}
 
 
 def plan_functions():

@@ -1132,33 +1132,34 @@ class _Engine:
 
     def _build_bwd_cstack(self, pl, b, B, train, W, zsum, conv_bias_grad, early_reduce):
         """spatial conv + BN1 + ELU + temporal conv backward recomputed from the token rows (csrc/cstack_bwd.hip, round 5): y1 / z1 / dz1 / dy1 never
-        exist in HBM.  dWs on the second stream; BatchNorm1-backward sums as one partial row per sample, summed in a fixed order by the apply pass."""
+        exist in HBM.  The BatchNorm1-backward sums and the dWs slabs come from ONE recompute of the tiles (eegclip_cstack_bwd_stats_w2: one partial row per
+        workgroup, summed in a fixed order by the apply pass); the slab reduction runs beside the taps reduction on the second stream."""
         P, G, sums, bn = self.P, self.G, b["sums"], b["bn"]
         dev = self.device
         if "csw_ws" not in b:
             b["csw_ws"] = torch.empty(int(lib().eegclip_cstack_bwd_w2_workspace_floats(B, N_CH)), dtype=torch.float32, device=dev)
             b["csb_ws"] = torch.empty(int(lib().eegclip_cstack_bwd_workspace_floats(B)), dtype=torch.float32, device=dev)
-            b["cs_rows3"] = torch.empty(B, 2 * C_TS, dtype=torch.float64, device=dev)
+            b["cs_rows3"] = torch.empty(int(lib().eegclip_cstack_bwd_rows_count(B, N_CH)), 2 * C_TS, dtype=torch.float64, device=dev)
         xs = (_p(b["n3"]), L_TOK * D_MODEL, D_MODEL)
         bnp = (_p(bn[0]), _p(bn[1]), _p(P[_TS + "2.weight"]), _p(P[_TS + "2.bias"]))
-        pl.call("eegclip_cstack_bwd_w2", *xs, _p(P[_TS + "0.weight"]), _p(P[_TS + "0.bias"]), *bnp, _p(b["dy2"]), _p(G[_TS + "4.weight"]), _p(b["csw_ws"]),
-                B, N_CH, side=True)
         rows3 = b["cs_rows3"]
+        nrows3 = rows3.shape[0]
         count1 = float(W * B * N_CH * W_TS)
         common = dict(B=B, H=N_CH, x=xs[0], xs_b=xs[1], xs_h=xs[2], w25=_p(P[_TS + "0.weight"]), bias1=_p(P[_TS + "0.bias"]), mean1=bnp[0], rstd1=bnp[1],
                       gamma1=bnp[2], beta1=bnp[3], packed_t=_p(self.cs_packed_t), dy2=_p(b["dy2"]), rows_out=_p(rows3), count=count1,
                       dgamma=_p(G[_TS + "2.weight"]), dbeta=_p(G[_TS + "2.bias"]), dx=_p(b["dn3"]), dw_partials=_p(b["csb_ws"]), dw25=_p(G[_TS + "0.weight"]))
-        pl.call_desc("eegclip_cstack_bwd_stats", _abi.CstackBwdDesc(stat=None, nstat=0, stat_local=None, nstat_local=0, **common))
-        stat, nstat, local, nlocal = _p(rows3), B, None, 0
+        pl.call_desc("eegclip_cstack_bwd_stats_w2", _abi.CstackBwdDesc(stat=None, nstat=0, stat_local=None, nstat_local=0, **common), _p(b["csw_ws"]))
+        stat, nstat, local, nlocal = _p(rows3), nrows3, None, 0
         if W > 1 or not train:
-            pl.call("eegclip_bn_finalize_rows", _p(rows3), B, count1, EPS, 0.1, C_TS, None, None, None, None, None, _p(sums[3]))
-            local, nlocal = _p(rows3), B
+            pl.call("eegclip_bn_finalize_rows", _p(rows3), nrows3, count1, EPS, 0.1, C_TS, None, None, None, None, None, _p(sums[3]))
+            local, nlocal = _p(rows3), nrows3
             if W > 1:
                 pl.callback(lambda: self._allreduce(sums[3]), "allreduce_bn1_bwd")
             stat, nstat = (_p(sums[3]), 1) if train else (_p(zsum), 1)
             if not train:
                 pl.callback(conv_bias_grad(_TS + "0.bias", _TS + "2.weight", bn[1], sums[3]), "conv1_bias_grad_eval")
-        # (the tap gradient leaves the apply pass as one partial row per sample; their sum is read by the optimizer only: second stream)
+        # (the tap gradient leaves the apply pass as one partial row per sample, dWs left the sums pass as slabs; their sums are read by the optimizer only:
+        #  second stream, one fork)
         pl.call_desc("eegclip_cstack_bwd_apply", _abi.CstackBwdDesc(stat=stat, nstat=nstat, stat_local=local, nstat_local=nlocal, **dict(common, dw25=None)))
         pl.early_cut = len(pl.ops)          # every gradient of the early bucket (loss scale, conv stack, head) has been ISSUED once the ops before this index
         #                                     and the taps reduction below have: the step plan starts their optimizer update here (step_plan.py)
@@ -1166,6 +1167,8 @@ class _Engine:
         def taps():
             pl.taps_op = len(pl.ops)
             pl.call("eegclip_cstack_bwd_taps_reduce", _p(b["csb_ws"]), B, _p(G[_TS + "0.weight"]), side=True)
+            pl.call("eegclip_cstack_w2_reduce", _p(b["csw_ws"]), B, N_CH, _p(G[_TS + "4.weight"]), side=True)
+            pl.taps_n = 2                    # (the step plan moves the two together)
         if early_reduce:
             taps()
         else:

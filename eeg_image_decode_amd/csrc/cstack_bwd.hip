@@ -6,8 +6,10 @@
 //                                * E[w][t] = sum_c dy1[c][w] taps[c][t]  (the accumulator tiles ARE the operand), overlap-added through a wave-private LDS
 //                                  tile into dS[j = 5w + t], transposed box filter -> the token-row gradient dx[b][h][:]
 //                                * dW1[c][t] += sum_w dy1[c][w] S[h][5w + t]: dy1 transposed through a wave-private packed LDS tile
-//   cstack_bwd_w2_kernel       dWs[o][c][h] = sum_{b,w} dy2[b][o][w] z1[b][c][h][w]: workgroup = (4 token rows, sample group), a wave owns ONE row h of
-//                              every sample of its group: y1^T tile -> z1^T in registers = the k = w operand; per-group slabs + an ordered reduction
+//   cstack_bwd_rows_kernel     <DWS> dWs[o][c][h] = sum_{b,w} dy2[b][o][w] z1[b][c][h][w]: workgroup = (2 token rows, 4 sample sub-groups), a wave owns ONE row h
+//                              of every sample of its group: xhat^T tile -> z1^T in registers = the k = w operand; per-group slabs + an ordered reduction
+//                              <SUMS> the BatchNorm1-backward sums from the same tiles: one partial row per WORKGROUP (the training plans: one recompute,
+//                              cstack_bwd_kernel<false> stays for callers that want one row per sample)
 //   cstack_pack_t_kernel       Ws (40,40,H) -> Ws^T fragments (rows = filters c, k = out channels o), once per optimizer step
 // Replaces sconv_bwd_w (+ reduce), sconv_bwd_x<stats> (+ colsum), sconv_bwd_x<apply> (dy1 write, 93 MB), tsconv_bwd_w (+ reduce), tsconv_bwd_x.
 #include "cstack_common.h"
@@ -465,30 +467,89 @@ __global__ __launch_bounds__(256) void cstack_w2_reduce_kernel(const float* __re
 //   k-step) of dWs[o][c] += sum_w dy2[b][o][w] z1[c][w]; the dy2 fragments (rows o, the same k slots) come from global memory, 16 bytes per quarter.
 // workgroup = (2 token rows, 4 sample sub-groups): the sub-groups' tiles are summed in LDS in a fixed order, so only SG <= 8 slabs [SG][H][40 o][40 c]
 // leave (3.2 MB; 32 slabs of one group each cost a 72-us reduction in the step), summed by cstack_w2_reduce_kernel, a tiled transpose to dWs[o][c][h].
+//
+// SUMS: the same wave also does the BatchNorm1-backward sums of its (row, samples).  The tap contraction yields xhat^T (taps scaled by rstd, (bias - mean) *
+// rstd in the ones slot) and u = gamma * xhat + beta is one packed fma; dz1^T[w][c] = sum_o dy2[o][w] Ws[o][c][h] lands in the same D[w][c] layout: A = dy2 as the
+// k = out-channel operand (the split halves the dWs product already holds, transposed through the wave's slice of `tile` as packed words [40 o][36 w]), B = row h
+// of packed_t, loaded ONCE per wave (the sample-major sums pass reloads it for every row of every sample).  da = dz1 * ELU'(u) (ELU' from ELU's own exp); sum da
+// and sum da * xhat stay in registers over the wave's samples; the workgroup's eight waves meet in LDS in wave order and leave as ONE fp64 partial row
+// [sum da | sum da * xhat] per workgroup: row index blockIdx.y * gridDim.x + blockIdx.x, eegclip_cstack_bwd_rows_count(B, H) rows in all.
 constexpr int CSW_NW = 8;                                      // 2 token rows x 4 sample sub-groups per workgroup
-__global__ __launch_bounds__(64 * CSW_NW) void cstack_bwd_w2_kernel(const float* __restrict__ x, long long xs_b, long long xs_h, const float* __restrict__ w25,
-                                                                    const float* __restrict__ bias1, const float* __restrict__ mean1,
-                                                                    const float* __restrict__ rstd1, const float* __restrict__ gamma1,
-                                                                    const float* __restrict__ beta1, const float* __restrict__ dy2, float* __restrict__ slabs,
-                                                                    int B, int H, int SG, int vec2) {
+struct cs_rows_args {
+    const float* x;
+    long long xs_b, xs_h;
+    const float *w25, *bias1, *mean1, *rstd1, *gamma1, *beta1;
+    const unsigned char* packed_t;                             // (SUMS)
+    const float* dy2;
+    float* slabs;                                              // (DWS)
+    double* rows_out;                                          // (SUMS)
+    int B, H, SG, vec2;
+};
+template <bool SUMS, bool DWS>
+__global__ __launch_bounds__(64 * CSW_NW) void cstack_bwd_rows_kernel(const cs_rows_args a) {
     EEG_LDS_BASE(unsigned char, ldsb);
     const int t = threadIdx.x, lane = t & 63, wv = wave_uniform(t >> 6);
     const int n = lane & 15, kg = lane >> 4;
+    const int B = a.B, H = a.H;
     unsigned* srow = reinterpret_cast<unsigned*>(ldsb) + wv * (CS_RS + 256);      // the wave's packed row + its prefix-sum scratch
     float* pscr = reinterpret_cast<float*>(srow + CS_RS);
     float* tile = reinterpret_cast<float*>(ldsb) + CSW_NW * (CS_RS + 256);       // [8 waves][1600]: the sub-groups' results before they are summed
-    const int G = 4 * SG;                                      // sample groups in all: wave (row, q) walks the samples g = 4 sg + q, g + G, ...
+    unsigned* dyt = reinterpret_cast<unsigned*>(tile) + wv * CS_C * CS_C;         // (SUMS) until then: the sample's dy2 as packed words [40 o][36 w]
+    unsigned char* tails = reinterpret_cast<unsigned char*>(tile + CSW_NW * CS_C * CS_C);      // (SUMS) [2 rows][3 ct][tail hi | tail lo] of packed_t
+    unsigned char* tapl = tails + 2 * 3 * 1024;                                                // (SUMS) [3 ct][hi | lo] tap fragments
+    const int G = 4 * a.SG;                                    // sample groups in all: wave (row, q) walks the samples g = 4 sg + q, g + G, ...
     const int h = 2 * blockIdx.x + (wv & 1), g = 4 * blockIdx.y + (wv >> 1);
     const bool active = h < H && g < B;                        // (a last row block may be short, a small batch may not fill the sub-groups)
     const f32x4 zero4{0.f, 0.f, 0.f, 0.f};
     f32x4 acc[3][3];                                          // D[o = 16 ot + 4 kg + r][c = 16 ct + n]
+    f32x2_t s1[3], s2[3];                                     // (SUMS) this lane's share of sum da, sum da * xhat of filter c = 16 ct + n
 #pragma unroll
-    for (int ot = 0; ot < 3; ++ot)
+    for (int ot = 0; ot < 3; ++ot) {
 #pragma unroll
         for (int ct = 0; ct < 3; ++ct) acc[ot][ct] = zero4;
+        s1[ot] = f32x2_t{0.f, 0.f};
+        s2[ot] = f32x2_t{0.f, 0.f};
+    }
+    if (SUMS) {
+        // the Ws^T tail fragments (out channels 32 .. 39) of the workgroup's two rows and the tap fragments (the same for every wave) go through LDS: resident
+        // beside the main Ws^T fragments they spill
+        if (wv == CSW_NW - 1) {
+            bf16x8 wh[3], wl[3];
+            cs_tap_frags_affine(a.w25, [&](int c, float& sc, float& sh) { sc = a.rstd1[c]; sh = (a.bias1[c] - a.mean1[c]) * sc; }, wh, wl);
+#pragma unroll
+            for (int ct = 0; ct < 3; ++ct) {
+                *reinterpret_cast<bf16x8*>(tapl + ct * 2048 + 16 * lane) = wh[ct];
+                *reinterpret_cast<bf16x8*>(tapl + ct * 2048 + 1024 + 16 * lane) = wl[ct];
+            }
+        }
+        if (t < 2 * 3 * 64 && 2 * blockIdx.x + t / 192 < H) {
+            const int row = t / 192, ct = (t % 192) >> 6, part = t & 63;
+            const unsigned char* src = a.packed_t + (long long)(2 * blockIdx.x + row) * CST_ROW + ct * CST_TILE + 2048 + 16 * part;
+            *reinterpret_cast<u32x4_t*>(tails + (row * 3 + ct) * 1024 + 16 * part) = *reinterpret_cast<const u32x4_t*>(src);
+        }
+        __syncthreads();
+    }
     if (active) {
+        const float *x = a.x, *dy2 = a.dy2;
+        const long long xs_b = a.xs_b, xs_h = a.xs_h;
+        const int vec2 = a.vec2;
+        // taps scaled by rstd with (bias - mean) * rstd in the ones slot: the contraction yields xhat itself, u = gamma * xhat + beta is one packed fma
         bf16x8 wh[3], wl[3];
-        cs_tap_frags_affine(w25, [&](int c, float& sc, float& sh) { sc = gamma1[c] * rstd1[c]; sh = beta1[c] + (bias1[c] - mean1[c]) * sc; }, wh, wl);
+        if (!SUMS) cs_tap_frags_affine(a.w25, [&](int c, float& sc, float& sh) { sc = a.rstd1[c]; sh = (a.bias1[c] - a.mean1[c]) * sc; }, wh, wl);
+        float Gm[3], Bt[3];
+        bf16x8 th_[3], tl_[3];                                // (SUMS) Ws^T fragments of row h: resident for the whole sample loop
+#pragma unroll
+        for (int ct = 0; ct < 3; ++ct) {
+            const int c = 16 * ct + n;
+            const float gm = c < CS_C ? a.gamma1[c] : 0.f, bt = c < CS_C ? a.beta1[c] : 0.f;      // (filters >= 40: u = 0, z1 = 0 as before)
+            Gm[ct] = gm;
+            Bt[ct] = bt;
+            if (SUMS) {
+                const unsigned char* base = a.packed_t + (long long)h * CST_ROW + ct * CST_TILE;
+                th_[ct] = *reinterpret_cast<const bf16x8*>(base + 16 * lane);
+                tl_[ct] = *reinterpret_cast<const bf16x8*>(base + 1024 + 16 * lane);
+            }
+        }
         float vx[4];
         f32x4 vd[3][3];
         auto load_sample = [&](int b) {
@@ -516,20 +577,92 @@ __global__ __launch_bounds__(64 * CSW_NW) void cstack_bwd_w2_kernel(const float*
                 x3_split4(vd[ot][2][0], vd[ot][2][1], vd[ot][2][2], vd[ot][2][3], a_, b_);
                 eh[ot] = cs_half_frag(a_);
                 el[ot] = cs_half_frag(b_);
+                if (SUMS && 16 * ot + n < CS_C) {
+                    // the same halves re-paired into (hi << 16) | lo words: dy2[o = 16 ot + n][w] of this sample, read back below with w as the row
+                    const u32x4_t Hh = __builtin_bit_cast(u32x4_t, dh[ot]), Ll = __builtin_bit_cast(u32x4_t, dl[ot]);
+                    unsigned* d = dyt + (16 * ot + n) * CS_W;
+                    *reinterpret_cast<u32x4_t*>(d + 4 * kg) = u32x4_t{cs_pair_lo(Hh[0], Ll[0]), cs_pair_hi(Hh[0], Ll[0]), cs_pair_lo(Hh[1], Ll[1]), cs_pair_hi(Hh[1], Ll[1])};
+                    *reinterpret_cast<u32x4_t*>(d + 16 + 4 * kg) = u32x4_t{cs_pair_lo(Hh[2], Ll[2]), cs_pair_hi(Hh[2], Ll[2]), cs_pair_lo(Hh[3], Ll[3]), cs_pair_hi(Hh[3], Ll[3])};
+                    if (kg == 0) *reinterpret_cast<u32x4_t*>(d + 32) = u32x4_t{cs_pair_lo(a_[0], b_[0]), cs_pair_hi(a_[0], b_[0]), cs_pair_lo(a_[1], b_[1]), cs_pair_hi(a_[1], b_[1])};
+                }
             }
-            if (b + G < B) load_sample(b + G);                // the next sample's loads land under this sample's MFMAs
+            if (b + G < B) load_sample(b + G);       // the next sample's loads land under this sample's MFMAs
             wave_sync();
             f32x2_t z[3][3][2];                               // z1^T[w = 16 wt + 4 kg + r][c = 16 ct + n]
 #pragma unroll
             for (int wt = 0; wt < 3; ++wt) {
                 bf16x8 xh, xl;
                 cs_sfrag_ones(srow, 0, wt, xh, xl);
-                f32x4 u[3] = {zero4, zero4, zero4};
-                cs_mma3_b3(xh, xl, wh, wl, u);                // u^T = BN1(y1)^T
+                f32x4 xhat[3] = {zero4, zero4, zero4}, dz[3] = {zero4, zero4, zero4};
+                if (SUMS) {
+                    const unsigned char* wp = tapl + 16 * lane + cs_opaque_zero();
 #pragma unroll
-                for (int ct = 0; ct < 3; ++ct) { z[wt][ct][0] = cs_elu2(cs_lo2(u[ct])); z[wt][ct][1] = cs_elu2(cs_hi2(u[ct])); }
+                    for (int ct = 0; ct < 3; ++ct) {
+                        wh[ct] = *reinterpret_cast<const bf16x8*>(wp + ct * 2048);
+                        wl[ct] = *reinterpret_cast<const bf16x8*>(wp + ct * 2048 + 1024);
+                    }
+                }
+                cs_mma3_b3(xh, xl, wh, wl, xhat);             // xhat^T = ((y1 - mean) * rstd)^T
+                if (SUMS) {
+                    // dy2 as the k = out-channel operand: row w = 16 wt + n, k slot j <-> o = 16 (j >> 2) + 4 kg + (j & 3); tail o = 32 + 4 kg + j (zero from o = 40);
+                    // positions >= 36: zero rows, so dz1 and da are exact zeros there
+                    // (ONE address register for all of it: the masked-out reads -- w >= 36, o >= 40 -- are not clamped, they land on later words of the
+                    //  slices / the tails region, inside the allocation, and are discarded)
+                    const bool wok = wt < 2 || 32 + n < CS_W;
+                    const unsigned* sp = dyt + 4 * kg * CS_W + n + 16 * wt;
+                    unsigned w8[8], w4[4];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) { const unsigned v = sp[(16 * (j >> 2) + (j & 3)) * CS_W]; w8[j] = wok ? v : 0u; }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { const unsigned v = sp[(32 + j) * CS_W]; w4[j] = (wok && kg < 2) ? v : 0u; }
+                    bf16x8 ah, al;
+                    cs_words_to_frags(w8, ah, al);
+                    const bf16x8 a2h = cs_frag(cs_pair_hi(w4[1], w4[0]), cs_pair_hi(w4[3], w4[2]), 0u, 0u);
+                    const bf16x8 a2l = cs_frag(cs_pair_lo(w4[1], w4[0]), cs_pair_lo(w4[3], w4[2]), 0u, 0u);
+                    const unsigned char* tp = tails + (wv & 1) * 3072 + 8 * lane + cs_opaque_zero();       // (opaque: the loads stay here, see cstack_common.h)
+                    bf16x8 uh8[3], ul8[3];
+#pragma unroll
+                    for (int ct = 0; ct < 3; ++ct) {
+                        uh8[ct] = cs_half_frag(*reinterpret_cast<const u32x2_t*>(tp + ct * 1024));
+                        ul8[ct] = cs_half_frag(*reinterpret_cast<const u32x2_t*>(tp + ct * 1024 + 512));
+                    }
+                    cs_mma3_b3(ah, al, th_, tl_, dz);         // dz1^T = dy2^T Ws[:, :, h], out channels 0 .. 31
+                    cs_mma3_b3(a2h, a2l, uh8, ul8, dz);       //                            out channels 32 .. 39
+                }
+#pragma unroll
+                for (int ct = 0; ct < 3; ++ct)
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const f32x2_t xk = k ? cs_hi2(xhat[ct]) : cs_lo2(xhat[ct]);
+                        const f32x2_t u = cs_fma2(xk, f32x2_t{Gm[ct], Gm[ct]}, f32x2_t{Bt[ct], Bt[ct]});
+                        f32x2_t mneg;
+                        const f32x2_t e = cs_elu_grad2(u, mneg);                                         // ELU'(u), and the exp of ELU(u) (cs_elu2's arithmetic)
+                        z[wt][ct][k] = cs_fma2(mneg, f32x2_t{-CS_LN2, -CS_LN2}, u) + (e + f32x2_t{-1.f, -1.f});
+                        if (SUMS) {
+                            const f32x2_t da = (k ? cs_hi2(dz[ct]) : cs_lo2(dz[ct])) * e;                 // da = dz1 * ELU'(u)
+                            s1[ct] += da;
+                            s2[ct] = cs_fma2(da, xk, s2[ct]);
+                        }
+                    }
             }
-            wave_sync();                                      // the row is consumed: the next sample may overwrite it
+            if (SUMS) {
+                // the dWs product's dy2 fragments (rows o, k = w) come back from the words this lane stored -- the same bits: held in registers across the
+                // three position tiles they are 48 VGPRs at the kernel's pressure peak (spills)
+#pragma unroll
+                for (int ot = 0; ot < 3; ++ot) {
+                    const bool ok = 16 * ot + n < CS_C;
+                    const unsigned* d = dyt + (16 * ot + n) * CS_W;                                      // (not clamped: see above)
+                    u32x4_t m0 = *reinterpret_cast<const u32x4_t*>(d + 4 * kg), m1 = *reinterpret_cast<const u32x4_t*>(d + 16 + 4 * kg);
+                    u32x4_t m2 = *reinterpret_cast<const u32x4_t*>(d + 32);
+                    if (!ok) { m0 = u32x4_t{0u, 0u, 0u, 0u}; m1 = m0; }
+                    if (!ok || kg != 0) m2 = u32x4_t{0u, 0u, 0u, 0u};
+                    const unsigned w8[8] = {m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
+                    cs_words_to_frags(w8, dh[ot], dl[ot]);
+                    eh[ot] = cs_frag(cs_pair_hi(m2[1], m2[0]), cs_pair_hi(m2[3], m2[2]), 0u, 0u);
+                    el[ot] = cs_frag(cs_pair_lo(m2[1], m2[0]), cs_pair_lo(m2[3], m2[2]), 0u, 0u);
+                }
+            }
+            wave_sync();                                      // the row (and the dy2 words) are consumed: the next sample may overwrite them
 #pragma unroll
             for (int ct = 0; ct < 3; ++ct) {
                 bf16x8 zh, zl;
@@ -554,15 +687,36 @@ __global__ __launch_bounds__(64 * CSW_NW) void cstack_bwd_w2_kernel(const float*
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int o = 16 * ot + 4 * kg + r, c = 16 * ct + n;
-                if (o < CS_C && c < CS_C) tile[wv * CS_C * CS_C + o * CS_C + c] = acc[ot][ct][r];      // (idle waves: zeros)
+                if (DWS && o < CS_C && c < CS_C) tile[wv * CS_C * CS_C + o * CS_C + c] = acc[ot][ct][r];      // (idle waves: zeros)
             }
-    __syncthreads();
-    for (int i = t; i < 2 * CS_C * CS_C; i += 64 * CSW_NW) {
-        const int row = i / (CS_C * CS_C), oc = i % (CS_C * CS_C), hh = 2 * blockIdx.x + row;
-        if (hh < H) {
-            const float* p = tile + row * CS_C * CS_C + oc;
-            slabs[((long long)blockIdx.y * H + hh) * CS_C * CS_C + oc] = ((p[0] + p[2 * CS_C * CS_C]) + p[4 * CS_C * CS_C]) + p[6 * CS_C * CS_C];
+    if (SUMS) {
+        // the lane groups kg hold disjoint positions w of the same filters: two butterflies, then [sum da (48) | sum da * xhat (48)] in the wave's own row region
+        float* sc = reinterpret_cast<float*>(srow);
+#pragma unroll
+        for (int ct = 0; ct < 3; ++ct) {
+            float u = s1[ct][0] + s1[ct][1], v = s2[ct][0] + s2[ct][1];
+#pragma unroll
+            for (int msk = 16; msk <= 32; msk <<= 1) { u += __shfl_xor(u, msk, 64); v += __shfl_xor(v, msk, 64); }
+            if (kg == 0) { sc[16 * ct + n] = u; sc[48 + 16 * ct + n] = v; }
         }
+    }
+    __syncthreads();
+    if (DWS) {
+        for (int i = t; i < 2 * CS_C * CS_C; i += 64 * CSW_NW) {
+            const int row = i / (CS_C * CS_C), oc = i % (CS_C * CS_C), hh = 2 * blockIdx.x + row;
+            if (hh < H) {
+                const float* p = tile + row * CS_C * CS_C + oc;
+                a.slabs[((long long)blockIdx.y * H + hh) * CS_C * CS_C + oc] = ((p[0] + p[2 * CS_C * CS_C]) + p[4 * CS_C * CS_C]) + p[6 * CS_C * CS_C];
+            }
+        }
+    }
+    if (SUMS && t < 2 * CS_C) {                               // the eight waves in order (idle waves: exact zeros)
+        const int which = t / CS_C, c = t % CS_C;
+        const float* sc = reinterpret_cast<const float*>(ldsb) + which * 48 + c;
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < CSW_NW; ++k) s += (double)sc[k * (CS_RS + 256)];
+        a.rows_out[((long long)blockIdx.y * gridDim.x + blockIdx.x) * 2 * CS_C + t] = s;
     }
 }
 
@@ -573,6 +727,8 @@ using namespace eeg;
 static int csb_vec2(const float* x, long long xs_b, long long xs_h) {
     return ((reinterpret_cast<uintptr_t>(x) & 7u) == 0 && (xs_b & 1) == 0 && (xs_h & 1) == 0) ? 1 : 0;
 }
+constexpr size_t CSW_LDS = (size_t)CSW_NW * (CS_RS + 256) * 4 + (size_t)CSW_NW * CS_C * CS_C * 4;      // (+ CSW_TAILS with SUMS)
+constexpr size_t CSW_TAILS = 2 * 3 * 1024 + 3 * 2048;       // Ws^T tails of two rows + the tap fragments
 static int csw_groups(int B) { const int sg = (B + 3) / 4; return sg < 8 ? sg : 8; }      // slabs: 32 row blocks x 8 x 8 waves = 2 waves per SIMD
 
 extern "C" long long eegclip_cstack_packed_t_bytes(int H) { return (H < 1 || H > CS_MAXH) ? 0 : (long long)H * CST_ROW; }
@@ -643,9 +799,31 @@ extern "C" int eegclip_cstack_bwd_w2(const float* x, long long xs_b, long long x
     if (!x || !w25 || !bias1 || !mean1 || !rstd1 || !gamma1 || !beta1 || !dy2 || !dWs || !workspace || B < 1 || H < 1 || H > CS_MAXH) return EEGCLIP_EINVAL;
     if (reinterpret_cast<uintptr_t>(dy2) & 15u) return EEGCLIP_EALIGN;
     const int G = csw_groups(B);
-    const size_t lds = (size_t)CSW_NW * (CS_RS + 256) * 4 + (size_t)CSW_NW * CS_C * CS_C * 4;
-    EEG_LAUNCH(cstack_bwd_w2_kernel, dim3((H + 1) / 2, G), dim3(64 * CSW_NW), lds, stream, x, xs_b, xs_h, w25, bias1, mean1, rstd1, gamma1, beta1, dy2, workspace, B,
-               H, G, csb_vec2(x, xs_b, xs_h));
+    const cs_rows_args ra{x, xs_b, xs_h, w25, bias1, mean1, rstd1, gamma1, beta1, nullptr, dy2, workspace, nullptr, B, H, G, csb_vec2(x, xs_b, xs_h)};
+    EEG_LAUNCH((cstack_bwd_rows_kernel<false, true>), dim3((H + 1) / 2, G), dim3(64 * CSW_NW), CSW_LDS, stream, ra);
     EEG_LAUNCH(cstack_w2_reduce_kernel, dim3(CS_C * CS_C / 32, (H + 31) / 32), dim3(256), 32 * 33 * sizeof(float), stream, (const float*)workspace, G, H, dWs);
+    return (int)hipGetLastError();
+}
+
+// one partial row [sum da | sum da * xhat] per workgroup of the row-major kernel
+extern "C" long long eegclip_cstack_bwd_rows_count(int B, int H) { return (B < 1 || H < 1 || H > CS_MAXH) ? 0 : (long long)((H + 1) / 2) * csw_groups(B); }
+
+// BatchNorm1-backward sums AND the spatial-conv weight-gradient slabs from one recompute of the tiles (cstack_bwd_rows_kernel<true, true>); the slabs are
+// summed by eegclip_cstack_w2_reduce, a launch of its own: only the optimizer reads dWs
+extern "C" int eegclip_cstack_bwd_stats_w2(const eegclip_cstack_bwd_desc* d, float* w2_slabs, void* stream) {
+    if (int rc = csb_check(d)) return rc;
+    if (!d->rows_out || !w2_slabs) return EEGCLIP_EINVAL;
+    if (reinterpret_cast<uintptr_t>(d->rows_out) & 7u) return EEGCLIP_EALIGN;
+    if (reinterpret_cast<uintptr_t>(d->dy2) & 15u) return EEGCLIP_EALIGN;
+    const int G = csw_groups(d->B);
+    const cs_rows_args ra{d->x, d->xs_b, d->xs_h, d->w25, d->bias1, d->mean1, d->rstd1, d->gamma1, d->beta1, static_cast<const unsigned char*>(d->packed_t), d->dy2,
+                          w2_slabs, d->rows_out, d->B, d->H, G, csb_vec2(d->x, d->xs_b, d->xs_h)};
+    EEG_LAUNCH((cstack_bwd_rows_kernel<true, true>), dim3((d->H + 1) / 2, G), dim3(64 * CSW_NW), CSW_LDS + CSW_TAILS, stream, ra);
+    return (int)hipGetLastError();
+}
+
+extern "C" int eegclip_cstack_w2_reduce(const float* slabs, int B, int H, float* dWs, void* stream) {
+    if (!slabs || !dWs || B < 1 || H < 1 || H > CS_MAXH) return EEGCLIP_EINVAL;
+    EEG_LAUNCH(cstack_w2_reduce_kernel, dim3(CS_C * CS_C / 32, (H + 31) / 32), dim3(256), 32 * 33 * sizeof(float), stream, slabs, csw_groups(B), H, dWs);
     return (int)hipGetLastError();
 }

@@ -261,6 +261,7 @@ class StepPlan:
         self._plan_adamw(optimizer, eng)
         early_cut = getattr(self.bwd, "early_cut", None) if self.adam_early else None
         taps_op = getattr(self.bwd, "taps_op", None)
+        taps_n = getattr(self.bwd, "taps_n", 1)                     # (the small reductions that go with it: consecutive ops, one fork)
         if early_cut is None or (taps_op is not None and taps_op < early_cut):
             early_cut = None
         b0 = len(pl.ops)
@@ -281,12 +282,13 @@ class StepPlan:
             pl._seed_slots += [(self.bwd_index[i], j) for i0, j in self.bwd._seed_slots if i0 == i]
 
         for i in range(len(self.bwd.ops)):
-            if (early_cut is not None and i == taps_op) or i == fuse_op:
+            if (early_cut is not None and taps_op is not None and taps_op <= i < taps_op + taps_n) or i == fuse_op:
                 continue                                     # (moved in front of the early update / behind the join, into the optimizer launch)
             emit_bwd(i)
             if early_cut is not None and i == early_cut - 1:
                 if taps_op is not None:
-                    emit_bwd(taps_op)
+                    for k in range(taps_n):
+                        emit_bwd(taps_op + k)
                 self._emit_adamw(pl, self.adam_early, side=True)
         pl.set_arg(self.bwd_index[self.bwd.dout_op], 0, self.da.data_ptr())
         if self.on_planes:

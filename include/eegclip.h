@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 22
+#define EEGCLIP_ABI_VERSION 23
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -1093,6 +1093,15 @@ int eegclip_cstack_bwd_taps_reduce(const float* dw_partials, int B, float* dw25,
 long long eegclip_cstack_bwd_w2_workspace_floats(int B, int H);
 int eegclip_cstack_bwd_w2(const float* x, long long xs_b, long long xs_h, const float* w25, const float* bias1, const float* mean1, const float* rstd1,
                           const float* gamma1, const float* beta1, const float* dy2, float* dWs, float* workspace, int B, int H, void* stream);
+/* (ABI 23) the BatchNorm1-backward sums and the weight-gradient slabs from ONE recompute of the tiles:
+ *   eegclip_cstack_bwd_stats_w2   d->rows_out receives eegclip_cstack_bwd_rows_count(B, H) partial rows [sum da (40) | sum da * xhat (40)] (fp64, one per
+ *                                 workgroup; their column sums are those of eegclip_cstack_bwd_stats' B rows: feed them to eegclip_cstack_bwd_apply as
+ *                                 stat / nstat = rows_count), w2_slabs (eegclip_cstack_bwd_w2_workspace_floats(B, H) floats) the per-group slabs of dWs.
+ *                                 Bit-reproducible, no atomics, nothing to clear.  Same argument checks as eegclip_cstack_bwd_stats and eegclip_cstack_bwd_w2.
+ *   eegclip_cstack_w2_reduce      dWs[o][c][h] += the slabs summed in a fixed order (the second launch of eegclip_cstack_bwd_w2, as an op of its own) */
+long long eegclip_cstack_bwd_rows_count(int B, int H);
+int eegclip_cstack_bwd_stats_w2(const eegclip_cstack_bwd_desc* d, float* w2_slabs, void* stream);
+int eegclip_cstack_w2_reduce(const float* slabs, int B, int H, float* dWs, void* stream);
 
 /* ---- reconstruction metrics without a pretrained network (csrc/recon_metrics.hip; the reference's metrics notebooks under Generation/ (..._metrics_sub8.ipynb,
  * Reconstruction_Metrics_ATM.ipynb), which copy MindEye's Reconstruction_Metrics: PixCorr, SSIM, two-way identification).  (ABI 21.)

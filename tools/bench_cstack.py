@@ -72,6 +72,12 @@ res["bwd_stats_us"] = ev(lambda: chk(L.eegclip_cstack_bwd_stats(ctypes.byref(bd)
 res["bwd_apply_us"] = ev(lambda: chk(L.eegclip_cstack_bwd_apply(ctypes.byref(bd), st)))
 res["bwd_w2_us"] = ev(lambda: chk(L.eegclip_cstack_bwd_w2(x.data_ptr(), 64 * 250, 250, w25.data_ptr(), bias1.data_ptr(), mu.data_ptr(), rs.data_ptr(), g1.data_ptr(),
                                                              b1.data_ptr(), dy2.data_ptr(), dWs.data_ptr(), w2ws.data_ptr(), B, H, st)))
+# the sums and the dWs slabs from one recompute (the training plans), and the slab reduction that went with bwd_w2
+nrows = int(L.eegclip_cstack_bwd_rows_count(B, H))
+rows4 = torch.empty(nrows, 80, dtype=torch.float64, device=dev)
+bd.rows_out = rows4.data_ptr()
+res["bwd_stats_w2_us"] = ev(lambda: chk(L.eegclip_cstack_bwd_stats_w2(ctypes.byref(bd), w2ws.data_ptr(), st)))
+res["w2_reduce_us"] = ev(lambda: chk(L.eegclip_cstack_w2_reduce(w2ws.data_ptr(), B, H, dWs.data_ptr(), st)))
 print(json.dumps(res))
 if len(sys.argv) > 1:
     json.dump(res, open(sys.argv[1], "w"), indent=1)
