@@ -637,19 +637,19 @@ class _Engine:
                 pl.call("eegclip_gather_rows", _p(b["h"]) + 4 * D_MODEL, L_TOK * D_MODEL, _p(b["hs"]) + 4 * D_MODEL, L_TOK * D_MODEL, _p(b["perm"]), B,
                         N_CH * D_MODEL, 1)
             tok = P[_TOK_SHARED] if shared else P[_TOK_TABLE]
-            pl.call("eegclip_embed_finish", _p(b["h"]), _p(tok), None if shared else _p(b["ids"]), B, L_TOK, D_MODEL, pe_, 0, SITE_EMBED, seed_at=7)
+            pl.call("eegclip_embed_finish", _p(b["h"]), _p(tok), None if shared else _p(b["ids"]), B, L_TOK, D_MODEL, pe_, 0, SITE_EMBED, seeded=True)
             # A2: fused QKV projection (weights adjacent in the flat buffer) + attention      (SelfAttention_Family.py:199-213)
             pl.gemm(R, 3 * HE, D_MODEL, _p(b["h"]), D(D_MODEL), D(1), _p(P[_LY + "attention.query_projection.weight"]), D(1), D(D_MODEL),
                     _p(b["qkv"]), D(3 * HE), D(1), bias_n=_p(P[_LY + "attention.query_projection.bias"]))
             pl.call("eegclip_attention_fwd", _p(b["qkv"]), _p(b["ctx"]), B, L_TOK, N_HEADS, D_HEAD, 3 * HE, 1.0 / math.sqrt(D_HEAD), pe_, 0,
-                    SITE_ATTN, seed_at=9)
+                    SITE_ATTN, seeded=True)
             # (dropout + residual of both sublayers live in the LayerNorm kernel that follows, not in the GEMM epilogue: one Philox block per 4
             #  consecutive columns there, one per ELEMENT in an MFMA accumulator layout -- 12 us per GEMM)
             pl.gemm(R, D_MODEL, HE, _p(b["ctx"]), D(HE), D(1), _p(P[_LY + "attention.out_projection.weight"]), D(1), D(HE),
                     _p(b["r1"]), D(D_MODEL), D(1), bias_n=_p(P[_LY + "attention.out_projection.bias"]))
             # A3: post-LN encoder layer + final LN      (Transformer_EncDec.py:45-51,77-78)
             pl.call("eegclip_residual_layernorm_fwd", _p(b["r1"]), _p(b["h"]), _p(b["r1"]), pe_, 0, SITE_ATTN_OUT, _p(P[_LY + "norm1.weight"]),
-                    _p(P[_LY + "norm1.bias"]), _p(b["n1"]), _p(b["mu1"]), _p(b["rs1"]), None, None, None, None, None, R, D_MODEL, EPS, seed_at=4)
+                    _p(P[_LY + "norm1.bias"]), _p(b["n1"]), _p(b["mu1"]), _p(b["rs1"]), None, None, None, None, None, R, D_MODEL, EPS, seeded=True)
             pl.gemm(R, D_FF, D_MODEL, _p(b["n1"]), D(D_MODEL), D(1), _p(P[_LY + "conv1.weight"]), D(1), D(D_MODEL), _p(b["g1"]), D(D_FF), D(1),
                     Cpre=_p(b["f1"]), bias_n=_p(P[_LY + "conv1.bias"]), act=ACT_GELU, drop_p=pe_, drop_site=SITE_FFN_ACT)
             pl.gemm(R, D_MODEL, D_FF, _p(b["g1"]), D(D_FF), D(1), _p(P[_LY + "conv2.weight"]), D(1), D(D_FF), _p(b["r2"]), D(D_MODEL), D(1),
@@ -657,7 +657,7 @@ class _Engine:
             # norm2 and the encoder's final norm back to back in one launch
             pl.call("eegclip_residual_layernorm_fwd", _p(b["r2"]), _p(b["n1"]), _p(b["r2"]), pe_, 0, SITE_FFN_OUT, _p(P[_LY + "norm2.weight"]),
                     _p(P[_LY + "norm2.bias"]), _p(b["n2"]), _p(b["mu2"]), _p(b["rs2"]), _p(P["encoder.encoder.norm.weight"]),
-                    _p(P["encoder.encoder.norm.bias"]), _p(b["n3"]), _p(b["mu3"]), _p(b["rs3"]), R, D_MODEL, EPS, seed_at=4)
+                    _p(P["encoder.encoder.norm.bias"]), _p(b["n3"]), _p(b["mu3"]), _p(b["rs3"]), R, D_MODEL, EPS, seeded=True)
         # A4+A5: tokens 0..62 -> box filter + 25-tap stride-5 conv (= conv + avg-pool) -> BN -> ELU      (ATMS_retrieval.py:91,102-105)
         sums, bn = b["sums"], b["bn"]
         bn2_rows = None
@@ -681,23 +681,23 @@ class _Engine:
                 b["gup"] = torch.empty(2, B, P_DIM, dtype=torch.bfloat16, device=self.device)
             rows_args = (_p(bn2_rows), B, float(B * W_TS), EPS, 0.1, _p(bn[2]), _p(bn[3]), *run2) if bn2_rows is not None else \
                 (None, 0, 1.0, EPS, 0.1, _p(bn[2]), _p(bn[3]), None, None, None)
-            # riders (arguments 23 / 24): the head weights' plane split by extra workgroups of this launch; the step plan adds the loss targets
+            # riders: the head weights' plane split by extra workgroups of this launch; the step plan puts its own table, with the loss targets, in their place
             pl.rider_items = (_abi.SplitItem * 4)()
             pl.rider_items[0] = self._head_weight_planes()
             pl._keep.append(pl.rider_items)
             pl.rider_op = len(pl.ops)
             pl.call("eegclip_proj1x1_fwd_rows_planes", _p(b["y2"]), *rows_args, _p(P[_TS + "5.weight"]), _p(P[_TS + "5.bias"]),
                     _p(P["enc_eeg.0.projection.0.weight"]), _p(P["enc_eeg.0.projection.0.bias"]), _p(b["z2"]), _p(b["feat"]), B, pc_, 0, SITE_CONV,
-                    _p(b["featp"][0]), _p(b["featp"][1]), pl.rider_items, 1, seed_at=19)
+                    _p(b["featp"][0]), _p(b["featp"][1]), riders=pl.rider_items, n_riders=1, seeded=True)
         elif bn2_rows is not None:
             # (the BatchNorm2 finalize rides in this kernel's prologue: the batch statistics as the per-sample partial rows eegclip_cstack_fwd left)
             pl.call("eegclip_proj1x1_fwd_rows", _p(b["y2"]), _p(bn2_rows), B, float(B * W_TS), EPS, 0.1, _p(bn[2]), _p(bn[3]), *run2,
                     _p(P[_TS + "5.weight"]), _p(P[_TS + "5.bias"]), _p(P["enc_eeg.0.projection.0.weight"]), _p(P["enc_eeg.0.projection.0.bias"]),
-                    _p(b["z2"]), _p(b["feat"]), B, pc_, 0, SITE_CONV, seed_at=19)
+                    _p(b["z2"]), _p(b["feat"]), B, pc_, 0, SITE_CONV, seeded=True)
         else:
             pl.call("eegclip_proj1x1_fwd", _p(b["y2"]), _p(bn[2]), _p(bn[3]), _p(P[_TS + "5.weight"]), _p(P[_TS + "5.bias"]),
                     _p(P["enc_eeg.0.projection.0.weight"]), _p(P["enc_eeg.0.projection.0.bias"]), _p(b["z2"]), _p(b["feat"]), B, pc_, 0, SITE_CONV,
-                    seed_at=11)
+                    seeded=True)
         pl.head_planes = head_planes
         if head_planes:
             # A6: projection head      (:157-167) on the K-parallel plane GEMM (csrc/head_gemm.hip, round 6): M = B is small, so K is split over workgroups --
@@ -711,11 +711,12 @@ class _Engine:
             pl.call("eegclip_head_act", *sl1, _p(P["proj_eeg.0.bias"]), _p(b["u"]), _p(b["gu"]), *gp, B, P_DIM)
             sl2 = self._head_gemm(pl, b, "hslab2", gp, P_DIM, self.hw["w2"], P_DIM, B)
             # s = u + dropout(W gelu(u) + b), out = LayerNorm(s): ResidualAdd + LayerNorm of Proj_eeg in one launch; `out` is a fresh tensor per call
-            # (argument 8 is patched by forward()); arguments 19 / 20: out again as planes (the step plan's loss operand)
+            # (forward() patches `y`); y_hi / y_lo: out again as planes (the step plan's loss operand)
             pl.out_op = len(pl.ops)
             pl.call("eegclip_residual_layernorm_fwd_slabs", sl2[0], _p(b["u"]), _p(b["s"]), pp_, 0, SITE_PROJ, _p(P["proj_eeg.2.weight"]),
-                    _p(P["proj_eeg.2.bias"]), 0, _p(b["mu4"]), _p(b["rs4"]), None, None, None, None, None, B, P_DIM, EPS, None, None, sl2[1], sl2[2],
-                    _p(P["proj_eeg.1.fn.1.bias"]), seed_at=4)
+                    _p(P["proj_eeg.2.bias"]), y=0, mean=_p(b["mu4"]), rstd=_p(b["rs4"]), gamma2=None, beta2=None, y2=None, mean2=None, rstd2=None,
+                    rows=B, cols=P_DIM, eps=EPS, y_hi=None, y_lo=None, nslabs=sl2[1], slab_stride=sl2[2], x_bias=_p(P["proj_eeg.1.fn.1.bias"]),
+                    seeded=True)
             return pl
         # A6 on fp32 operands (exact-fp32 plans): a 4 x 16 tile grid cannot fill 256 CUs and each workgroup walks K = 1440
         # serially, so the products are split over K (atomics into a zeroed buffer) and bias/GELU/dropout/residual run as a tiny epilogue.
@@ -734,10 +735,11 @@ class _Engine:
                     bias_n=_p(P["proj_eeg.1.fn.1.bias"]))
             w_lin = b["s"]
         # s = u + dropout(W gelu(u) + b), out = LayerNorm(s): ResidualAdd + LayerNorm of Proj_eeg in one launch; `out` is a fresh tensor per
-        # call (argument 8 is patched by forward()), so callers keep what they are handed and no copy is made
+        # call (forward() patches `y`), so callers keep what they are handed and no copy is made
         pl.out_op = len(pl.ops)
         pl.call("eegclip_residual_layernorm_fwd", _p(w_lin), _p(b["u"]), _p(b["s"]), pp_, 0, SITE_PROJ, _p(P["proj_eeg.2.weight"]),
-                _p(P["proj_eeg.2.bias"]), 0, _p(b["mu4"]), _p(b["rs4"]), None, None, None, None, None, B, P_DIM, EPS, seed_at=4)
+                _p(P["proj_eeg.2.bias"]), y=0, mean=_p(b["mu4"]), rstd=_p(b["rs4"]), gamma2=None, beta2=None, y2=None, mean2=None, rstd2=None,
+                rows=B, cols=P_DIM, eps=EPS, seeded=True)
         return pl
 
     def _cstack_enabled(self, pl):
@@ -860,15 +862,16 @@ class _Engine:
         head_side_ops = []
         if head_planes:
             # (round 6) the head's backward on the K-parallel plane GEMM.  The upstream gradient may itself be the partial slabs of the loss's query-gradient
-            # GEMM (arguments 1 / 2, patched by the step plan); the LayerNorm backward leaves ds, dv = ds * mask / (1 - p) (fp32: the weight gradients'
+            # GEMM (nslabs / slab_stride, patched by the step plan); the LayerNorm backward leaves ds, dv = ds * mask / (1 - p) (fp32: the weight gradients'
             # operands), dv again as planes (the next GEMM's A operand) and the summed upstream gradient for its parameter half
             if "dvp" not in b:
                 b["dvp"] = torch.empty(2, B, P_DIM, dtype=torch.bfloat16, device=self.device)
                 b["dup"] = torch.empty(2, B, P_DIM, dtype=torch.bfloat16, device=self.device)
                 b["dout_sum"] = torch.empty(B, P_DIM, dtype=torch.float32, device=self.device)
             vp, up = (_p(b["dvp"][0]), _p(b["dvp"][1])), (_p(b["dup"][0]), _p(b["dup"][1]))
-            pl.call("eegclip_layernorm_bwd_slabs", 0, 1, 0, _p(b["s"]), _p(P["proj_eeg.2.weight"]), _p(b["mu4"]), _p(b["rs4"]), _p(b["ds"]), B, P_DIM,
-                    _p(b["dv"]), *vp, None, pp_, 0, SITE_PROJ, seed_at=15)
+            pl.call("eegclip_layernorm_bwd_slabs", dy=0, nslabs=1, slab_stride=0, x=_p(b["s"]), gamma=_p(P["proj_eeg.2.weight"]), mean=_p(b["mu4"]),
+                    rstd=_p(b["rs4"]), dx=_p(b["ds"]), rows=B, cols=P_DIM, dx_drop=_p(b["dv"]), dd_hi=vp[0], dd_lo=vp[1], dy_sum=None, drop_p=pp_, seed=0,
+                    site=SITE_PROJ, seeded=True)
             # the head's second-stream launches (LayerNorm parameter half, the two weight gradients: operands dv | gu and du | feat stay untouched until the
             # optimizer) are emitted TOGETHER in front of the conv stack's backward, next to its own second-stream launch: ONE fork instead of three -- every
             # fork idles the main queue for ~7 us (tools/step_timeline.py)
@@ -925,10 +928,10 @@ class _Engine:
             if "pj_bn_rows" not in b:
                 b["pj_bn_rows"] = torch.empty(B, 2 * C_TS, dtype=torch.float64, device=self.device)
             pl.call("eegclip_proj1x1_bwd_rows", *dfeat_slabs, _p(b["z2"]), _p(P["enc_eeg.0.projection.0.weight"]), _p(b["y2"]), _p(bn[2]), _p(bn[3]),
-                    _p(P[_TS + "5.weight"]), _p(P[_TS + "5.bias"]), _p(b["dz2"]), _p(b["pj_ws"]), _p(b["pj_bn_rows"]), B, pc_, 0, SITE_CONV, seed_at=15)
+                    _p(P[_TS + "5.weight"]), _p(P[_TS + "5.bias"]), _p(b["dz2"]), _p(b["pj_ws"]), _p(b["pj_bn_rows"]), B, pc_, 0, SITE_CONV, seeded=True)
             pl.call("eegclip_bn_elu_bwd_apply_rows", _p(b["dz2"]), _p(b["y2"]), _p(bn[2]), _p(bn[3]), _p(P[_TS + "5.weight"]), _p(P[_TS + "5.bias"]),
                     _p(b["pj_bn_rows"]), B, 2 * C_TS, 0, float(B * W_TS),
-                    _p(b["dy2"]), _p(G[_TS + "5.weight"]), _p(G[_TS + "5.bias"]), B, C_TS, W_TS, pc_, 0, SITE_CONV, seed_at=18)
+                    _p(b["dy2"]), _p(G[_TS + "5.weight"]), _p(G[_TS + "5.bias"]), B, C_TS, W_TS, pc_, 0, SITE_CONV, seeded=True)
             for f in head_side_ops:
                 f()
             pl.call("eegclip_proj1x1_bwd_reduce", _p(b["pj_ws"]), B, _p(G["enc_eeg.0.projection.0.weight"]), _p(G["enc_eeg.0.projection.0.bias"]), None, side=True)
@@ -936,11 +939,11 @@ class _Engine:
             if dfeat_slabs is not None:
                 pl.call("eegclip_proj1x1_bwd_slabs", *dfeat_slabs, _p(b["z2"]), _p(P["enc_eeg.0.projection.0.weight"]), _p(b["y2"]), _p(bn[2]), _p(bn[3]),
                         _p(P[_TS + "5.weight"]), _p(P[_TS + "5.bias"]), _p(b["dz2"]), _p(G["enc_eeg.0.projection.0.weight"]),
-                        _p(G["enc_eeg.0.projection.0.bias"]), _p(sums[2]), _p(b["pj_ws"]), B, pc_, 0, SITE_CONV, seed_at=17)
+                        _p(G["enc_eeg.0.projection.0.bias"]), _p(sums[2]), _p(b["pj_ws"]), B, pc_, 0, SITE_CONV, seeded=True)
             else:
                 pl.call("eegclip_proj1x1_bwd", _p(b["dfeat"]), _p(b["z2"]), _p(P["enc_eeg.0.projection.0.weight"]), _p(b["y2"]), _p(bn[2]), _p(bn[3]),
                         _p(P[_TS + "5.weight"]), _p(P[_TS + "5.bias"]), _p(b["dz2"]), _p(G["enc_eeg.0.projection.0.weight"]),
-                        _p(G["enc_eeg.0.projection.0.bias"]), _p(sums[2]), _p(b["pj_ws"]), B, pc_, 0, SITE_CONV, seed_at=15)
+                        _p(G["enc_eeg.0.projection.0.bias"]), _p(sums[2]), _p(b["pj_ws"]), B, pc_, 0, SITE_CONV, seeded=True)
             local2 = None
             if W > 1:
                 local2 = torch.zeros_like(sums[2])
@@ -954,7 +957,7 @@ class _Engine:
                 pl.callback(conv_bias_grad(_TS + "4.bias", _TS + "5.weight", bn[3], sums[2]), "conv2_bias_grad_eval")
             pl.call("eegclip_bn_elu_bwd_apply", _p(b["dz2"]), _p(b["y2"]), _p(bn[2]), _p(bn[3]), _p(P[_TS + "5.weight"]), _p(P[_TS + "5.bias"]),
                     _p(sums[2]) if train else _p(zsum), (_p(local2) if local2 is not None else None) if train else _p(sums[2]), float(W * B * W_TS), _p(b["dy2"]), _p(G[_TS + "5.weight"]), _p(G[_TS + "5.bias"]), B, C_TS,
-                    W_TS, pc_, 0, SITE_CONV, seed_at=16)
+                    W_TS, pc_, 0, SITE_CONV, seeded=True)
             for f in head_side_ops:
                 f()
         if self._cstack_bwd_enabled(pl):
@@ -1012,7 +1015,7 @@ class _Engine:
             pl.call("eegclip_token_block_bwd", ctypes.byref(bd), 0)
             pl.deferred.append(lambda: pl.call("eegclip_token_block_bwd", ctypes.byref(bd), 2, side=True))
             pl.call(attn_bwd, _p(b["qkv"]), _p(b["dctx"]), dqkvp, 1, B, L_TOK, N_HEADS, D_HEAD, 3 * HE, 1.0 / math.sqrt(D_HEAD),
-                    pe_, 0, SITE_ATTN, seed_at=11)
+                    pe_, 0, SITE_ATTN, seeded=True)
             pl.call("eegclip_token_block_bwd", ctypes.byref(bd), 1)
         else:
             # final LN, LN2
@@ -1022,7 +1025,7 @@ class _Engine:
             # bias gradients ride on the weight-gradient GEMMs; dropout' and gelu' of the hidden activation are the epilogue of the GEMM
             # that produces its gradient -- 5 elementwise / reduction passes over (B*64, 250..256) tensors gone
             pl.call("eegclip_layernorm_bwd_full", _p(b["dn2"]), _p(b["r2"]), _p(P[_LY + "norm2.weight"]), _p(b["mu2"]), _p(b["rs2"]), _p(b["dr2"]),
-                    _p(G[_LY + "norm2.weight"]), _p(G[_LY + "norm2.bias"]), R, D_MODEL, 0, _p(b["df2"]), pe_, 0, SITE_FFN_OUT, lnf_ws, seed_at=13)
+                    _p(G[_LY + "norm2.weight"]), _p(G[_LY + "norm2.bias"]), R, D_MODEL, 0, _p(b["df2"]), pe_, 0, SITE_FFN_OUT, lnf_ws, seeded=True)
             wgrad(_LY + "conv2.weight", _p(b["df2"]), D_MODEL, _p(b["g1"]), D_FF, D_MODEL, D_FF, R, bias=_LY + "conv2.bias")
             pl.gemm(R, D_FF, D_MODEL, _p(b["df2"]), D(D_MODEL), D(1), _p(P[_LY + "conv2.weight"]), D(D_FF), D(1), _p(b["dg1"]), D(D_FF), D(1),
                     act=ACT_GELU_GRAD, R=_p(b["f1"]), Rm=D(D_FF), Rn=D(1), drop_p=pe_, drop_site=SITE_FFN_ACT)                  # dg1 := df1
@@ -1031,16 +1034,16 @@ class _Engine:
                     accumulate=1)                                              # dr2 := dn1
             # attention block: r1 = h + dropout(Wo ctx + bo)
             pl.call("eegclip_layernorm_bwd_full", _p(b["dr2"]), _p(b["r1"]), _p(P[_LY + "norm1.weight"]), _p(b["mu1"]), _p(b["rs1"]), _p(b["dr1"]),
-                    _p(G[_LY + "norm1.weight"]), _p(G[_LY + "norm1.bias"]), R, D_MODEL, 0, _p(b["da1"]), pe_, 0, SITE_ATTN_OUT, lnf_ws, seed_at=13)
+                    _p(G[_LY + "norm1.weight"]), _p(G[_LY + "norm1.bias"]), R, D_MODEL, 0, _p(b["da1"]), pe_, 0, SITE_ATTN_OUT, lnf_ws, seeded=True)
             wgrad(_LY + "attention.out_projection.weight", _p(b["da1"]), D_MODEL, _p(b["ctx"]), HE, D_MODEL, HE, R,
                   bias=_LY + "attention.out_projection.bias")
             pl.gemm(R, HE, D_MODEL, _p(b["da1"]), D(D_MODEL), D(1), _p(P[_LY + "attention.out_projection.weight"]), D(HE), D(1), _p(b["dctx"]), D(HE), D(1))
             if attn_bwd == "eegclip_attention_bwd_x3":
                 pl.call(attn_bwd, _p(b["qkv"]), _p(b["dctx"]), _p(b["dqkv"]), 0, B, L_TOK, N_HEADS, D_HEAD, 3 * HE, 1.0 / math.sqrt(D_HEAD),
-                        pe_, 0, SITE_ATTN, seed_at=11)
+                        pe_, 0, SITE_ATTN, seeded=True)
             else:
                 pl.call(attn_bwd, _p(b["qkv"]), _p(b["dctx"]), _p(b["dqkv"]), B, L_TOK, N_HEADS, D_HEAD, 3 * HE, 1.0 / math.sqrt(D_HEAD),
-                        pe_, 0, SITE_ATTN, seed_at=10)
+                        pe_, 0, SITE_ATTN, seeded=True)
             wgrad(_LY + "attention.query_projection.weight", _p(b["dqkv"]), 3 * HE, _p(b["h"]), D_MODEL, 3 * HE, D_MODEL, R,
                   bias=_LY + "attention.query_projection.bias")                                    # q|k|v weights and biases are adjacent
             pl.gemm(R, D_MODEL, 3 * HE, _p(b["dqkv"]), D(3 * HE), D(1), _p(P[_LY + "attention.query_projection.weight"]), D(D_MODEL), D(1),
@@ -1079,7 +1082,7 @@ class _Engine:
                 if b["wk:embed_joint"].numel() < need:
                     b["wk:embed_joint"] = torch.empty(need, dtype=torch.float32, device=self.device)
                     for op in pl.j_wk_ops:
-                        pl.set_arg(op, 4, _p(b["wk:embed_joint"]))
+                        pl.set_arg(op, "workspace", _p(b["wk:embed_joint"]))
                 pl.j_wk_all = (_abi.WgradTokProblem * self.n_subj)(*pl.j_wk_arr)          # (the per-subject originals; j_wk_arr holds this batch's members)
                 pl._keep.append(pl.j_wk_all)
         elif not self.joint:
@@ -1116,7 +1119,7 @@ class _Engine:
         P, G = self.P, self.G
         # s = u + dropout(W4 gelu(u) + b4): the LayerNorm backward writes ds and dv = ds * mask / (1 - p) in one pass
         pl.call("eegclip_layernorm_bwd", 0, _p(b["s"]), _p(P["proj_eeg.2.weight"]), _p(b["mu4"]), _p(b["rs4"]), _p(b["ds"]),
-                None, None, B, P_DIM, 0, _p(b["dv"]), pp_, 0, SITE_PROJ, seed_at=13)
+                None, None, B, P_DIM, 0, _p(b["dv"]), pp_, 0, SITE_PROJ, seeded=True)
         # (the gamma / beta gradients of every LayerNorm are a second, independent kernel: it runs on the side stream, off the dX chain)
         pl.dout_par_op = len(pl.ops)
         pl.call("eegclip_layernorm_bwd", 0, _p(b["s"]), None, _p(b["mu4"]), _p(b["rs4"]), None,
@@ -1288,8 +1291,8 @@ class _Engine:
                 q.sample0, q.samples = st, n
                 pl.j_wk_arr[i] = q                           # struct copy: the members of this batch, in subject order
             for op in pl.j_wk_ops:
-                pl.set_arg(op, 1, len(segs))
-                pl.set_arg(op, 3, pl.j_wk_slices[len(segs)])
+                pl.set_arg(op, "n_prob", len(segs))
+                pl.set_arg(op, "slices", pl.j_wk_slices[len(segs)])
             if not has_dx:
                 return
         if in_order:
@@ -1297,7 +1300,7 @@ class _Engine:
             if not backward or has_dx:
                 skip.add(pl.j_scatter)
         if not backward:
-            pl.set_arg(pl.j_gather, 2, x_ptr)
+            pl.set_arg(pl.j_gather, "src", x_ptr)
             xb, hb = (x_ptr, _p(b["h"])) if in_order else (_p(b["xs"]), _p(b["hs"]))
             for s, st, n in segs:
                 d = pl.j_gemm[s]
@@ -1315,11 +1318,11 @@ class _Engine:
         if has_gemm:
             for i, (s, _, _) in enumerate(segs):
                 pl.j_arr[i] = pl.j_gemm[s]                   # struct copy: the members of this batch, in subject order
-            pl.set_arg(pl.j_group, 1, len(segs))
+            pl.set_arg(pl.j_group, "n", len(segs))
         if has_dx:
             for i, (s, _, _) in enumerate(segs):
                 pl.j_dx_arr[i] = pl.j_dx[s]
-            pl.set_arg(pl.j_dx_group, 1, len(segs))
+            pl.set_arg(pl.j_dx_group, "n", len(segs))
         pl.skip = frozenset(skip)
 
     def forward(self, x, ids, shared, train, host_ids=None):
@@ -1347,7 +1350,7 @@ class _Engine:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if train and max(probs) > 0 else 0
         b["seed"] = seed
         out = torch.empty(B, P_DIM, dtype=torch.float32, device=self.device)
-        pl.set_arg(pl.out_op, 8, out.data_ptr())
+        pl.set_arg(pl.out_op, "y", out.data_ptr())
         pl.run(raw_stream(), seed)
         if getattr(pl, "clears_zb", False):
             b["zb_clean"] = True
@@ -1425,8 +1428,8 @@ class _Engine:
             self.plans[pk] = self._build_bwd(B, shared, probs, want_dx, early, train)
         pl = self.plans[pk]
         self.attach_grads(shared, {s for s, _, _ in b["segs"]} if self.joint else ())
-        pl.set_arg(pl.dout_op, 0, dout.data_ptr())
-        pl.set_arg(pl.dout_par_op, 0, dout.data_ptr())
+        pl.set_arg(pl.dout_op, "dy", dout.data_ptr())
+        pl.set_arg(pl.dout_par_op, "dy", dout.data_ptr())
         pl._keep_x = (x, dout)
         if self.joint:
             self._joint_layout(pl, b, B, None, x.data_ptr(), True)

@@ -59,12 +59,33 @@ class Plan:
         self._c_skip = ()
         self.use_c_executor = True      # (False: the Python executor below -- timed runs always take it; tools set it for host-time comparisons)
 
-    # -- generic positional op; `seed_at` = index of the seed argument (patched at run time)
-    def call(self, fname, *args, seed_at=None, side=False):
-        fn = getattr(self.L, fname)
-        self.ops.append((fn, list(args) + [None], fname, side))
-        if seed_at is not None:
-            self._seed_slots.append((len(self.ops) - 1, seed_at))
+    def call(self, fname, *args, seeded=False, side=False, **named):
+        """an op by entry-point name.  Arguments are those of include/eegclip.h without the trailing stream: positional, the rest by the header's
+        parameter names.  `seeded`: the parameter named `seed` takes the run's dropout seed.  A wrong count or name raises here, when the plan is built."""
+        params = _abi.plan_params(fname)
+        if named:
+            rest = params[len(args):]
+            bad = [k for k in named if k not in rest]
+            if bad:
+                raise TypeError(f"{fname}: {bad[0]!r} is {'given twice' if bad[0] in params else 'not a parameter'}")
+            missing = [k for k in rest if k not in named]
+            if missing:
+                raise TypeError(f"{fname}: parameter {missing[0]!r} is missing")
+            args += tuple(named[k] for k in rest)
+        if len(args) != len(params):
+            raise TypeError(f"{fname} takes {len(params)} arguments before the stream ({', '.join(params)}), got {len(args)}")
+        self.ops.append((getattr(self.L, fname), list(args) + [None], fname, side))
+        if seeded:
+            self._seed_slots.append((len(self.ops) - 1, self.arg_index(fname, "seed")))
+
+    def arg_index(self, op, name):
+        """position of the parameter `name` of an entry point, given by its name or by the index of an op that calls it: for callers that patch the
+        same argument every step and resolve it once, when the plan is built"""
+        fname = self.ops[op][2] if isinstance(op, int) else op
+        try:
+            return _abi.ARG_INDEX[fname][name]
+        except KeyError:
+            raise KeyError(f"{fname} has no parameter {name!r}") from None
 
     def call_desc(self, fname, d, *extra, seeded=False, side=False):
         """an op whose first argument is a descriptor struct owned by the plan (`seeded`: its .seed field takes the run's dropout seed)"""
@@ -93,7 +114,7 @@ class Plan:
 
     def gemm_grouped(self, n_max, side=False):
         """one eegclip_gemm_f32_grouped op over a descriptor array the caller fills before each run: returns (array, op index); the member
-        count is op argument 1"""
+        count is the op's argument `n`"""
         arr = (_abi.GemmDesc * n_max)()
         self._keep.append(arr)
         self.ops.append((self.L.eegclip_gemm_f32_grouped, [arr, 0, None], "eegclip_gemm_f32_grouped", side))
@@ -117,8 +138,10 @@ class Plan:
     def op_names(self):
         return [op[2] for op in self.ops]
 
-    def set_arg(self, idx, j, value):
-        """patch argument j of op idx for the following runs (the per-call pointers: input batch, output tensor, upstream gradient)"""
+    def set_arg(self, idx, arg, value):
+        """patch an argument of op idx, given by the header's parameter name or by position, for the following runs (the per-call pointers: input
+        batch, output tensor, upstream gradient)"""
+        j = self.arg_index(idx, arg) if isinstance(arg, str) else arg
         self.ops[idx][1][j] = value
         if self._c is not None:
             self._c_write(idx, j, value)

@@ -226,7 +226,7 @@ class _PriorEngine:
             pl.gemm(N, ho, hi, xin, D(W), D(1), _p(P[st["l"] + "0.weight"]), D(1), D(hi), _p(b[f"lin{s}"]), D(ho), D(1),
                     bias_n=_p(P[st["l"] + "0.bias"]))
             pl.call("eegclip_layernorm_silu_fwd", _p(b[f"lin{s}"]), _p(P[st["l"] + "1.weight"]), _p(P[st["l"] + "1.bias"]), _p(b[f"ln{s}"]), _p(b[f"act{s}"]),
-                    _p(b[f"mu{s}"]), _p(b[f"rs{s}"]), N, ho, 1e-5, p, 0, s, seed_at=11)
+                    _p(b[f"mu{s}"]), _p(b[f"rs{s}"]), N, ho, 1e-5, p, 0, s, seeded=True)
             if st["dec"] is not None:
                 pl.call("eegclip_axpby", _p(b[skips[n_enc - 1 - st["dec"]]]), _p(b[f"act{s}"]), N * ho, 1.0, 1.0)     # x += hidden_activations[-1-j]
             cur = f"act{s}"
@@ -264,7 +264,7 @@ class _PriorEngine:
                 hoist.gemm(cond_rows, hi, Cd, _p(b["c"]), D(Cd), D(1), _p(P[st["c"] + "weight"]), D(1), D(Cd), _p(b[f"ce{s}"]), D(hi), D(1),
                            bias_n=_p(P[st["c"] + "bias"]))
         step = Plan(f"prior_step[N={N}]")
-        step.te_slots = []                   # (op index, stage, width): argument 5 of these ops is TE_stage + j * width floats
+        step.te_slots = []                   # (op index, stage, width): `te` of these ops is TE_stage + j * width floats
         n_st, n_enc = len(self.stages), m.num_layers - 1
 
         def finish(lin, gamma, beta, skip, act, nxt, rows_h):
@@ -272,8 +272,8 @@ class _PriorEngine:
             if nxt is None:
                 step.call("eegclip_prior_stage_infer", lin, gamma, beta, skip, act, None, None, 0, None, N, rows_h, 1e-5)
             else:
-                step.call("eegclip_prior_stage_infer", lin, gamma, beta, skip, act, _p(b[f"te{nxt}"]), _p(b[f"ce{nxt}"]) if cond_rows else None,
-                          cond_rows, _p(b[f"xin{nxt}"]), N, rows_h, 1e-5)
+                step.call("eegclip_prior_stage_infer", lin, gamma, beta, skip, act, te=_p(b[f"te{nxt}"]), ce=_p(b[f"ce{nxt}"]) if cond_rows else None,
+                          ce_rows=cond_rows, xin_out=_p(b[f"xin{nxt}"]), rows=N, cols=rows_h, eps=1e-5)
                 step.te_slots.append((idx, nxt, self.stages[nxt]["hin"]))
 
         step.gemm(N, h0, E, _p(b["x"]), D(E), D(1), _p(P["input_layer.0.weight"]), D(1), D(E), _p(b["linI"]), D(h0), D(1), bias_n=_p(P["input_layer.0.bias"]))
@@ -315,7 +315,7 @@ class _PriorEngine:
             st = self.stages[s]
             hi, ho = st["hin"], st["hout"]
             small = hi * ho < 256 * 256
-            pl.call("eegclip_silu_bwd", _p(b[f"dact{s}"]), _p(b[f"ln{s}"]), _p(b[f"dln{s}"]), N * ho, 0, p, 0, s, seed_at=6)
+            pl.call("eegclip_silu_bwd", _p(b[f"dact{s}"]), _p(b[f"ln{s}"]), _p(b[f"dln{s}"]), N * ho, 0, p, 0, s, seeded=True)
             pl.call("eegclip_layernorm_bwd", _p(b[f"dln{s}"]), _p(b[f"lin{s}"]), _p(P[st["l"] + "1.weight"]), _p(b[f"mu{s}"]), _p(b[f"rs{s}"]), _p(b[f"dlin{s}"]),
                     _p(G[st["l"] + "1.weight"]), _p(G[st["l"] + "1.bias"]), N, ho, 0, None, 0.0, 0, 0)
             wgrad(st["l"] + "0.weight", _p(b[f"dlin{s}"]), ho, _p(b["XIN"]) + 4 * self.col0[s], self.wide, ho, hi, small, bias=st["l"] + "0.bias")
@@ -438,7 +438,7 @@ class _PriorEngine:
             skip = _p(b[skips[n_enc - 1 - st["dec"]]]) if st["dec"] is not None else None          # x += hidden_activations[-1-j]
             pl.call("eegclip_prior_stage_fwd", _p(b[f"lin{s}"]), _p(P[st["l"] + "1.weight"]), _p(P[st["l"] + "1.bias"]), skip, _p(b[f"ln{s}"]), _p(b[f"act{s}"]),
                     _p(b[f"mu{s}"]), _p(b[f"rs{s}"]), b["actLP"][0].data_ptr() if last else None, b["actLP"][1].data_ptr() if last else None, N, ho, 1e-5, p, 0, s,
-                    seed_at=14)
+                    seeded=True)
             cur = f"act{s}"
         self._gp(pl, self._pl(b["actLP"]), h0, self._wplanes("output_layer.weight"), h0, N, E, h0, C=_p(b["out"]), ldc=E, bias=_p(P["output_layer.bias"]))
         return pl
@@ -479,7 +479,7 @@ class _PriorEngine:
             dl = self._pl(b[f"dlinP{s}"])
             ws = b.setdefault(f"psb_ws{s}", torch.empty(int(lib().eegclip_prior_stage_bwd_workspace_floats(N, ho)), dtype=torch.float32, device=self.device))
             pl.call("eegclip_prior_stage_bwd", _p(b[f"dact{s}"]), _p(b[f"ln{s}"]), _p(b[f"lin{s}"]), _p(P[st["l"] + "1.weight"]), _p(b[f"mu{s}"]), _p(b[f"rs{s}"]),
-                    None, dl[0], dl[1], None, None, N, ho, p, 0, s, _p(ws), seed_at=14)
+                    None, dl[0], dl[1], None, None, N, ho, p, 0, s, _p(ws), seeded=True)
             pl.call("eegclip_prior_stage_bwd_params", _p(ws), N, ho, _p(G[st["l"] + "1.weight"]), _p(G[st["l"] + "1.bias"]), side=True)
             # dxin = dlin W: as planes (operand of the time-embedding dX GEMM and of three weight gradients); in the same epilogue the gradient w.r.t.
             # the previous activation = dxin (+ the skip branch for encoder stages: decode stage j = n_enc-1-i adds skips[i])
@@ -604,11 +604,11 @@ class _TrainStepPlan:
             pl._seed_slots += [(base + i, j) for i, j in src._seed_slots]
             pl._seed_descs += src._seed_descs
         self.noise_op = len(pl.ops)
-        pl.call("eegclip_ddpm_add_noise", 0, _p(self.noise), _p(self.ts), _p(sa), _p(sb), _p(self.x), N, E)
+        pl.call("eegclip_ddpm_add_noise", h=0, noise=_p(self.noise), t=_p(self.ts), sqrt_acp=_p(sa), sqrt_1macp=_p(sb), out=_p(self.x), n=N, d=E)
         self.fwd = fwd
         splice(fwd)
         self.mse_op = len(pl.ops)
-        pl.call("eegclip_mse_loss_grad", _p(b["out"]), _p(self.noise), N * E, 0, _p(b["dout"]))
+        pl.call("eegclip_mse_loss_grad", _p(b["out"]), _p(self.noise), N * E, loss=0, dpred=_p(b["dout"]))
         splice(bwd)
         pl.join()
         pl.memset(sumsq)
@@ -619,7 +619,9 @@ class _TrainStepPlan:
         self.adam_ops = []
         for (p0, n, wp, gp, mp, vp, members) in fast["launch"]:
             self.adam_ops.append(len(pl.ops))
-            pl.call("eegclip_adamw_step_zero_grad", wp, gp, mp, vp, n, g["lr"], b1, b2, g["eps"], g["weight_decay"], 0, 1.0, _p(clip))
+            pl.call("eegclip_adamw_step_zero_grad", wp, gp, mp, vp, n, lr=g["lr"], beta1=b1, beta2=b2, eps=g["eps"], weight_decay=g["weight_decay"], step=0,
+                    grad_scale=1.0, grad_scale_dev=_p(clip))
+        self.lr_at, self.step_at = (pl.arg_index("eegclip_adamw_step_zero_grad", k) for k in ("lr", "step"))     # (patched per step)
         self.pl = pl
         self.group = g
 
@@ -634,16 +636,16 @@ class _TrainStepPlan:
         self.noise.normal_()                                   # torch.randn_like(h): the same generator call
         self.ts.random_(0, self.T)                             # torch.randint(0, T, (N,), device=...)
         tt.copy_(self.ts)                                      # the time embedding's fp32 timesteps
-        pl.set_arg(self.noise_op, 0, h.data_ptr())
-        pl.set_arg(self.mse_op, 3, loss_sum.data_ptr())
+        pl.set_arg(self.noise_op, "h", h.data_ptr())
+        pl.set_arg(self.mse_op, "loss", loss_sum.data_ptr())
         self.fwd.in_items[0].src = self.x.data_ptr()
         if cond:
             self.fwd.in_items[2].src = c.data_ptr()
         fast["run_steps"] = [st + 1 for st in fast["run_steps"]]
         fast["pending"] += 1
         for op, st in zip(self.adam_ops, fast["run_steps"]):
-            pl.set_arg(op, 5, g["lr"])
-            pl.set_arg(op, 10, st)
+            pl.set_arg(op, self.lr_at, g["lr"])
+            pl.set_arg(op, self.step_at, st)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0 else 0
         self.eng.bufs[N]["seed"] = seed
         pl._keep_step = (h, c, loss_sum)
@@ -918,7 +920,7 @@ class Pipe:
         j = 0
         for i, t in enumerate(steps):
             for idx, st, width in step.te_slots:
-                step.set_arg(idx, 5, b[f"te{st}"].data_ptr() + 4 * width * i)
+                step.set_arg(idx, "te", b[f"te{st}"].data_ptr() + 4 * width * i)
             step.run(stream)
             nz = None
             if t > 0:

@@ -153,8 +153,8 @@ class StepPlan:
             self.items[0] = self.fwd.rider_items[0]
             self.item0 = 1
             pl._keep.append(self.items)
-            pl.set_arg(self.fwd_base + self.fwd.rider_op, 23, self.items)
-            pl.set_arg(self.fwd_base + self.fwd.rider_op, 24, 1 + T_)
+            pl.set_arg(self.fwd_base + self.fwd.rider_op, "riders", self.items)
+            pl.set_arg(self.fwd_base + self.fwd.rider_op, "n_riders", 1 + T_)
         else:
             self.items = (_abi.SplitItem * 2)()
             self.item0 = 0
@@ -164,10 +164,7 @@ class StepPlan:
             self.items[self.item0 + i] = _abi.SplitItem(src=0, hi=self.t_planes[0, i * B:].data_ptr(), lo=self.t_planes[1, i * B:].data_ptr(), rows=B, cols=Dm,
                                                         ld_src=Dm, ld_out=Dm, transpose=0, copy=self.stack[i * B].data_ptr() if self.stack is not None else None,
                                                         ld_copy=Dm)
-        fn, args, name, side = pl.ops[self.out_op]
-        if name != "eegclip_residual_layernorm_fwd_slabs":
-            raise NotApplicable(f"unexpected output op {name}")
-        args[19], args[20] = self.q_planes[0].data_ptr(), self.q_planes[1].data_ptr()      # (the head's LayerNorm adds the second Linear's slabs; planes are arguments 19 / 20)
+        self._output_planes(pl)
         ws = int(L.eegclip_infonce_fused_workspace_floats(B, B))
         self.if_buf = torch.empty(2 * T_ * (ws + 2 * B), dtype=torch.float32, device=dev)
         if self.on_planes:
@@ -210,8 +207,7 @@ class StepPlan:
         pl.call_desc("eegclip_head_gemm", _abi.HeadGemmDesc(a_hi=self.q_planes[0].data_ptr(), a_lo=self.q_planes[1].data_ptr(), b_hi=self.class_planes[0].data_ptr(),
                                                            b_lo=self.class_planes[1].data_ptr(), lda=Dm, ldb=Dm, M=B, N=ncp, K=Dm, slices=1, slab_stride=0,
                                                            C=self.logits.data_ptr(), ldc=ncp), side=True)
-        self.count_op = len(pl.ops)
-        pl.call("eegclip_top1_count", self.logits.data_ptr(), B, n_classes, ncp, sc_ptr, 0, 0, side=True)
+        self._count_op(pl, B, n_classes, ncp, sc_ptr)
         self.small = self.on_planes and eloss.infonce_small_enabled(B, T_, self.planes)
         if self.small:
             # (round 6) one process at the training batch size: the raw logits of all targets as ONE K-parallel plane GEMM, then two row-block kernels
@@ -225,16 +221,16 @@ class StepPlan:
                                                                C=self.s_slabs.data_ptr(), ldc=NC))
             pl.call("eegclip_infonce_small_fwd", self.s_slabs.data_ptr(), S_, B * NC, B, T_, sc_ptr, self.s_ws.data_ptr())
             w4 = list(self.weights) + [0.0] * (4 - T_)
-            self.if_fwd_op, self.loss_arg = len(pl.ops), 11                 # (the op whose `loss` argument is patched per step)
-            pl.call("eegclip_infonce_small_grad", B, T_, sc_ptr, self.s_ws.data_ptr(), *w4, self.Gp[0].data_ptr(), self.Gp[1].data_ptr(), NC, 0,
-                    eng.G["logit_scale"].data_ptr())                        # d loss / d scale straight into its gradient
+            pl.call("eegclip_infonce_small_grad", B, T_, sc_ptr, self.s_ws.data_ptr(), *w4, self.Gp[0].data_ptr(), self.Gp[1].data_ptr(), NC, loss=0,
+                    dscale=eng.G["logit_scale"].data_ptr())                 # d loss / d scale straight into its gradient
         # (loss.fused_infonce's training form: the forward leaves the per-tile partials, the gradient pass finalises them itself and adds the loss)
         else:
             pl.call("eegclip_infonce_fused_fwd", arr, 2 * T_, B, B, Dm, self.planes, B, sc_ptr, None)
-            self.if_fwd_op, self.loss_arg = len(pl.ops), 8                  # (the op whose `loss` argument is patched per step)
-            pl.call("eegclip_infonce_fused_grad_finalize", garr, T_, B, B, Dm, self.planes, B, sc_ptr, 0, eng.G["logit_scale"].data_ptr())      # d loss / d scale straight into its gradient
+            pl.call("eegclip_infonce_fused_grad_finalize", garr, T_, B, B, Dm, self.planes, B, sc_ptr, loss=0,
+                    dscale=eng.G["logit_scale"].data_ptr())                 # d loss / d scale straight into its gradient
+        self.loss_slot = self._slot(pl, len(pl.ops) - 1, "loss")            # (patched per step: where the step's loss is accumulated)
         # dA = [G_img | G_txt] [img; txt]: one launch, K = T B
-        self.mse_op = None
+        self.mse_slots = None
         if self.on_planes:
             # ... K-parallel from planes (csrc/head_gemm.hip); the encoder's backward adds the slabs while its first kernel loads them
             S = int(L.eegclip_head_gemm_slices(B, Dm, T_ * B))
@@ -245,8 +241,8 @@ class StepPlan:
                                                                slab_stride=B * Dm, C=self.da.data_ptr(), ldc=Dm, b_kmajor=1))
             if self.mse_w:
                 # the MSE term: weight * mean((z - img)^2) added to the step's loss, its gradient = the LAST slab of the backward's upstream gradient
-                self.mse_op = len(pl.ops)
-                pl.call("eegclip_mse_loss_grad_scaled", 0, 0, B * Dm, self.mse_w, 0, self.da[S].data_ptr())
+                pl.call("eegclip_mse_loss_grad_scaled", pred=0, target=0, n=B * Dm, weight=self.mse_w, loss=0, dpred=self.da[S].data_ptr())
+                self.mse_slots = [self._slot(pl, len(pl.ops) - 1, k) for k in ("pred", "target", "loss")]
         else:
             self.da = torch.empty(B, Dm, dtype=torch.float32, device=dev)
             self.da_slices = 1
@@ -290,16 +286,19 @@ class StepPlan:
                     for k in range(taps_n):
                         emit_bwd(taps_op + k)
                 self._emit_adamw(pl, self.adam_early, side=True)
-        pl.set_arg(self.bwd_index[self.bwd.dout_op], 0, self.da.data_ptr())
+        pl.set_arg(self.bwd_index[self.bwd.dout_op], "dy", self.da.data_ptr())
         if self.on_planes:
             # the backward's first kernel adds the S slabs while it loads them and leaves the sum for the parameter half of the head's LayerNorm
             bb = eng.bufs[B]
-            pl.set_arg(self.bwd_index[self.bwd.dout_op], 1, self.da_slices)
-            pl.set_arg(self.bwd_index[self.bwd.dout_op], 2, B * Dm)
-            pl.set_arg(self.bwd_index[self.bwd.dout_op], 13, bb["dout_sum"].data_ptr())
-            pl.set_arg(self.bwd_index[self.bwd.dout_par_op], 0, bb["dout_sum"].data_ptr())
+            pl.set_arg(self.bwd_index[self.bwd.dout_op], "nslabs", self.da_slices)
+            pl.set_arg(self.bwd_index[self.bwd.dout_op], "slab_stride", B * Dm)
+            pl.set_arg(self.bwd_index[self.bwd.dout_op], "dy_sum", bb["dout_sum"].data_ptr())
+            pl.set_arg(self.bwd_index[self.bwd.dout_par_op], "dy", bb["dout_sum"].data_ptr())
         else:
-            pl.set_arg(self.bwd_index[self.bwd.dout_par_op], 0, self.da.data_ptr())
+            pl.set_arg(self.bwd_index[self.bwd.dout_par_op], "dy", self.da.data_ptr())
+        # joint-subject model: _joint_layout re-points the per-subject weight-gradient launches of the backward plan every step; run() mirrors their
+        # problem count and slice count onto this plan's copies: (this plan's op, backward-plan op, argument)
+        self.j_wk_mirror = [(self.bwd_index[op], op, self.bwd.arg_index(op, k)) for op in getattr(self.bwd, "j_wk_ops", ()) for k in ("n_prob", "slices")]
         pl.join()               # the optimizer reads every gradient (second-stream weight gradients) and rewrites logit_scale (read by the accuracy readout)
         # ---- fused AdamW + the zero_grad() that opens the next iteration (what the early update has not taken)
         if fuse_op is not None:
@@ -307,16 +306,15 @@ class StepPlan:
             (li, wp, gp, mp, vp, n), = late
             lr, b1, b2, eps, wd = self.hyper
             self.bwd_index[fuse_op] = len(pl.ops)
-            self.adam_ops.append((len(pl.ops), li, 10))
-            pl.call("eegclip_wgrad_tok_reduce_adamw", *args[:5], wp, gp, mp, vp, n, lr, b1, b2, eps, wd, 0)
+            self.adam_ops.append((len(pl.ops), li, *(pl.arg_index("eegclip_wgrad_tok_reduce_adamw", k) for k in ("lr", "step"))))
+            pl.call("eegclip_wgrad_tok_reduce_adamw", *args[:5], wp, gp, mp, vp, n, lr=lr, beta1=b1, beta2=b2, eps=eps, weight_decay=wd, step=0)
         else:
             self._emit_adamw(pl, late)
         self.pl = pl
         self._class_ptr = None
 
     def _build_data_parallel(self, model, optimizer, eng, pl, splice, B, n_classes, Dm, L, dev):
-        self.split_op = self.mse_op = None
-        self.if_fwd_op = None
+        self.split_op = self.mse_slots = self.loss_slot = None
         self._cur = {}
         pl.callback(lambda: model.loss_func.gather_targets(self._cur["img"], self._cur["txt"]), "allgather_targets")
         f0 = splice(self.fwd)
@@ -325,19 +323,15 @@ class StepPlan:
         sc_ptr = model.logit_scale.detach().reshape(1).data_ptr()
         ncp = (n_classes + 3) // 4 * 4
         self.q_planes = torch.empty(2, B, Dm, dtype=torch.bfloat16, device=dev)
-        fn, args, name, side = pl.ops[self.out_op]
-        if name != "eegclip_residual_layernorm_fwd_slabs":
-            raise NotApplicable(f"unexpected output op {name}")
-        args[19], args[20] = self.q_planes[0].data_ptr(), self.q_planes[1].data_ptr()
+        self._output_planes(pl)
         self.logits = torch.empty(B, ncp, dtype=torch.float32, device=dev)
         self.class_planes = torch.zeros(2, ncp, Dm, dtype=torch.bfloat16, device=dev)
         pl.call_desc("eegclip_head_gemm", _abi.HeadGemmDesc(a_hi=self.q_planes[0].data_ptr(), a_lo=self.q_planes[1].data_ptr(), b_hi=self.class_planes[0].data_ptr(),
                                                            b_lo=self.class_planes[1].data_ptr(), lda=Dm, ldb=Dm, M=B, N=ncp, K=Dm, slices=1, slab_stride=0,
                                                            C=self.logits.data_ptr(), ldc=ncp), side=True)
-        self.count_op = len(pl.ops)
-        pl.call("eegclip_top1_count", self.logits.data_ptr(), B, n_classes, ncp, sc_ptr, 0, 0, side=True)
+        self._count_op(pl, B, n_classes, ncp, sc_ptr)
         # ---- the loss between the collectives
-        b0_holder = {}
+        dy_slots = []
 
         def loss_cb():
             import types
@@ -349,15 +343,15 @@ class StepPlan:
             da, ds, _ = ctx.grads
             cur["da"] = da                                        # (alive until the backward has been enqueued)
             eng.G["logit_scale"].copy_(ds.reshape(eng.G["logit_scale"].shape))
-            pl.set_arg(b0_holder["b0"] + self.bwd.dout_op, 0, da.data_ptr())
-            pl.set_arg(b0_holder["b0"] + self.bwd.dout_par_op, 0, da.data_ptr())
+            for slot in dy_slots:                                 # (the upstream gradient of the spliced backward's two LayerNorm halves)
+                pl.set_arg(*slot, da.data_ptr())
         pl.callback(loss_cb, "clip_loss_data_parallel")
         # ---- encoder backward (its callbacks: SyncBN sums, the early bucket's asynchronous all-reduce)
         b0 = len(pl.ops)
-        b0_holder["b0"] = b0
         self.bwd_base = b0
         self.bwd_index = [b0 + i for i in range(len(self.bwd.ops))]
         splice(self.bwd)
+        dy_slots += [self._slot(pl, b0 + op, "dy") for op in (self.bwd.dout_op, self.bwd.dout_par_op)]
         from . import dist as edist
         pl.callback(lambda: edist.average_flat_grads(eng.gflat, eng), "allreduce_flat_gradient")
         pl.join()
@@ -373,7 +367,7 @@ class StepPlan:
         fast = optimizer._fast_last.get(0)
         self.fast = fast
         self.group = optimizer.param_groups[0]
-        self.adam_ops = []                # (plan op, index into fast["launch"], argument index of lr): hyper-parameters at lr .. lr + 4, the run's step count behind them -- patched per call
+        self.adam_ops = []                # (plan op, index into fast["launch"], position of `lr`, of `step`): lr, beta1, beta2, eps, weight_decay follow one another; they and the run's step count are patched per call
         self.adam_early, self.adam_late = [], []
         base, (a0, a1) = eng.flat.data_ptr(), eng.early_bucket
         for li, (p0, n, wp, gp, mp, vp, members) in enumerate(fast["launch"]):
@@ -415,8 +409,26 @@ class StepPlan:
         gs = None
         lr, b1, b2, eps, wd = self.hyper
         for li, wp, gp, mp, vp, n in launches:
-            self.adam_ops.append((len(pl.ops), li, 5))
-            pl.call("eegclip_adamw_step_zero_grad", wp, gp, mp, vp, n, lr, b1, b2, eps, wd, 0, 1.0, gs, side=side)
+            self.adam_ops.append((len(pl.ops), li, *(pl.arg_index("eegclip_adamw_step_zero_grad", k) for k in ("lr", "step"))))
+            pl.call("eegclip_adamw_step_zero_grad", wp, gp, mp, vp, n, lr=lr, beta1=b1, beta2=b2, eps=eps, weight_decay=wd, step=0, grad_scale=1.0,
+                    grad_scale_dev=gs, side=side)
+
+    @staticmethod
+    def _slot(pl, op, name):
+        """(op index, argument position) of a parameter that run() patches every step: the name is resolved here, once"""
+        return op, pl.arg_index(op, name)
+
+    def _output_planes(self, pl):
+        """the head's LayerNorm (it adds the second Linear's slabs) leaves the query features as planes too: the loss operand"""
+        if pl.ops[self.out_op][2] != "eegclip_residual_layernorm_fwd_slabs":
+            raise NotApplicable(f"unexpected output op {pl.ops[self.out_op][2]}")
+        pl.set_arg(self.out_op, "y_hi", self.q_planes[0].data_ptr())
+        pl.set_arg(self.out_op, "y_lo", self.q_planes[1].data_ptr())
+        self.out_slot = self._slot(pl, self.out_op, "y")
+
+    def _count_op(self, pl, B, n_classes, ncp, sc_ptr):
+        pl.call("eegclip_top1_count", self.logits.data_ptr(), B, n_classes, ncp, sc_ptr, labels=0, count=0, side=True)
+        self.labels_slot, self.count_slot = (self._slot(pl, len(pl.ops) - 1, k) for k in ("labels", "count"))
 
     def index_of(self, kind, i):
         """plan op index of op `i` of the spliced forward ("f") / backward ("b") plan (bench.py maps its per-launch timings through this)"""
@@ -473,7 +485,7 @@ class StepPlan:
             if optimizer.param_groups[0] is not g:
                 return False
             self.hyper = (g["lr"], b1, b2, g["eps"], g["weight_decay"])       # (a learning-rate schedule: patch the optimizer launches)
-            for op, _li, base in self.adam_ops:
+            for op, _li, base, _step in self.adam_ops:
                 for j, v in enumerate(self.hyper):
                     self.pl.set_arg(op, base + j, v)
         return all(p.grad is None for p in g["params"])
@@ -499,13 +511,12 @@ class StepPlan:
                 b["ids_uniform"] = uid
             eng._joint_layout(self.fwd, b, B, host, eeg_data.data_ptr(), False)
             eng._joint_layout(self.bwd, b, B, None, eeg_data.data_ptr(), True)
-            for op in self.bwd.j_wk_ops:
-                pl.set_arg(self.index_of("b", op), 1, self.bwd.ops[op][1][1])
-                pl.set_arg(self.index_of("b", op), 3, self.bwd.ops[op][1][3])
+            for idx, op, j in self.j_wk_mirror:
+                pl.set_arg(idx, j, self.bwd.ops[op][1][j])
         self.fwd.tb_desc.x = eeg_data.data_ptr()
         out = torch.empty(B, 1024, dtype=torch.float32, device=self.dev)
         op = out.data_ptr()
-        pl.set_arg(self.out_op, 8, op)
+        pl.set_arg(*self.out_slot, op)
         cp = (class_feats.data_ptr(), class_feats._version)
         if cp != self._class_ptr:                  # a new (or modified) class table: its planes, once
             nc = class_feats.shape[0]
@@ -515,8 +526,8 @@ class StepPlan:
             if rc:
                 raise RuntimeError(f"eegclip_split_rows returned {rc}")
             self._class_ptr = cp
-        pl.set_arg(self.count_op, 5, labels.data_ptr())
-        pl.set_arg(self.count_op, 6, correct.data_ptr())
+        pl.set_arg(*self.labels_slot, labels.data_ptr())
+        pl.set_arg(*self.count_slot, correct.data_ptr())
         if self.world > 1:
             self._cur = {"img": img, "txt": txt, "out": out}
         else:
@@ -529,17 +540,16 @@ class StepPlan:
         if eng._clear_for is None or eng._clear_for != eng._attached:
             eng.gflat.zero_()
         acc = _zero_pair(self.dev) if self.world == 1 else None
-        if self.if_fwd_op is not None:
-            pl.set_arg(self.if_fwd_op, self.loss_arg, acc.data_ptr())
-        if self.mse_op is not None:
-            pl.set_arg(self.mse_op, 0, op)
-            pl.set_arg(self.mse_op, 1, img.data_ptr())
-            pl.set_arg(self.mse_op, 4, acc.data_ptr())
+        if self.loss_slot is not None:
+            pl.set_arg(*self.loss_slot, acc.data_ptr())
+        if self.mse_slots is not None:
+            for slot, ptr in zip(self.mse_slots, (op, img.data_ptr(), acc.data_ptr())):
+                pl.set_arg(*slot, ptr)
         fast = self.fast
         fast["run_steps"] = [st + 1 for st in fast["run_steps"]]
         fast["pending"] += 1
-        for opi, li, base in self.adam_ops:
-            pl.set_arg(opi, base + 5, fast["run_steps"][li])
+        for opi, li, _lr, step_at in self.adam_ops:
+            pl.set_arg(opi, step_at, fast["run_steps"][li])
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if max(self.probs) > 0 else 0
         b["seed"] = seed
         pl._keep_step = (eeg_data, img, txt, labels, class_feats, out)      # (alive until the next step has been enqueued)
