@@ -12,6 +12,11 @@
 // k = 4 kx + c and zeros at c = 3 and kx >= 11.  The frame's rows are wide enough for the last window's 16 pixels (eegclip_convrelu16_in_width), so what the
 // zero weights meet is always a frame element: zero, or a pixel -- which must be finite: an Inf or NaN within 5 pixels right of a window reaches that window's
 // outputs as NaN (0 x Inf), where a convolution proper would not read it.
+//
+// The SwAV row's ResNet-50 trunk (torchvision's Bottleneck ResNet v1.5 up to `avgpool`) runs on the same convolution kernel with a second epilogue
+// (eegclip_convbn16: eval-mode BatchNorm as fp32 scale / shift, the block's residual added in fp32, ReLU or not) for 1 x 1 and 3 x 3 layers at stride 1 or 2 and
+// the 3-channel 7 x 7 stride-2 stem in the form above (a 3-pixel border, [64][7][64] weights; the 9 pixels right of a window must be finite), with
+// MaxPool2d(3, 2, 1), the average pool to fp32 (N, C) and scipy's correlation distance per pair of feature rows.
 #include "half16.h"
 
 namespace eeg {
@@ -29,11 +34,22 @@ struct mn_args {
     int Hop, Wop, opad, Cout;
     int KH, KW, kc, stride;            // k-tile kt = ((ky KW + kx) kc + c0) / 64 reads 64 elements from frame pixel (y stride + ky, x stride + kx), element c0
     int M, tiles_n, ntiles, chunk;
+    static constexpr bool BN = false;  // the epilogue: bias + ReLU
+};
+
+// eegclip_convbn16's arguments: the same tile loop with the epilogue act(scale[co] acc + shift[co] + residual).  A type of its own, so the kernel argument
+// block of the bias + ReLU instantiations stays what it was.
+struct mn_bn_args : mn_args {
+    const float* scale;                // [Cout]
+    const float* shift;                // [Cout]
+    const unsigned short* residual;    // NULL, or a frame in the output's own layout
+    int relu;
+    static constexpr bool BN = true;
 };
 
 // NJ: 32-column blocks per MFMA wave along N; the N tile is 64 NJ wide
-template <bool F16, int NJ>
-__global__ __launch_bounds__(512) void convrelu16_kernel(const mn_args a) {
+template <bool F16, int NJ, class ARGS>
+__global__ __launch_bounds__(512) void convrelu16_kernel(const ARGS a) {
     EEG_LDS_BASE(unsigned char, lds);
     constexpr int TN = 64 * NJ, STAGE_B = MN_A_B + TN * MN_ROWB;
     const int logical = (int)(blockIdx.x & 7) * a.chunk + (int)(blockIdx.x >> 3);
@@ -148,12 +164,24 @@ __global__ __launch_bounds__(512) void convrelu16_kernel(const mn_args a) {
 #pragma unroll
             for (int eq = 0; eq < 4; ++eq) {
                 const int n = n0 + wn * 32 * NJ + 32 * j + 8 * eq + 4 * h;
-                const u16x4 bv = *reinterpret_cast<const u16x4*>(a.bias + n);
                 u16x4 o;
+                if constexpr (ARGS::BN) {
+                    // eval-mode BatchNorm as fp32 scale / shift, the residual added in fp32, one rounding at the store
+                    u16x4 rv{0, 0, 0, 0};
+                    if (a.residual) rv = *reinterpret_cast<const u16x4*>(a.residual + opix + n);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float v = acc[j][i][4 * eq + e] + to_f32<F16>(bv[e]);
-                    o[e] = to_h<F16>(v < 0.f ? 0.f : v);      // ReLU (a NaN stays a NaN)
+                    for (int e = 0; e < 4; ++e) {
+                        float v = acc[j][i][4 * eq + e] * a.scale[n + e] + a.shift[n + e];
+                        if (a.residual) v += to_f32<F16>(rv[e]);
+                        o[e] = to_h<F16>(a.relu && v < 0.f ? 0.f : v);
+                    }
+                } else {
+                    const u16x4 bv = *reinterpret_cast<const u16x4*>(a.bias + n);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float v = acc[j][i][4 * eq + e] + to_f32<F16>(bv[e]);
+                        o[e] = to_h<F16>(v < 0.f ? 0.f : v);      // ReLU (a NaN stays a NaN)
+                    }
                 }
                 *reinterpret_cast<u16x4*>(a.out + opix + n) = o;
             }
@@ -186,7 +214,100 @@ __global__ __launch_bounds__(256) void maxpool16_kernel(const unsigned short* __
     }
 }
 
-// ---- (N, 3, H, W) planes -> the first layer's frame [N][H + 4][Wf][4]: pixel (y, x) at frame (y + 2, x + 2) as {c0, c1, c2, 0}; a copy of 16-bit patterns
+// ---- MaxPool2d(3, 2, padding=1), floor mode (ResNet's): the same thread shape.  A tap outside the image is skipped, not read (the frame's border, if any,
+// holds zeros, which would beat an all-negative window); the centre tap is always inside, so every window has a first tap.  Taps are visited in torch's
+// order and a later tap replaces the maximum only when larger (or NaN): the stored pattern is the largest tap's own.
+template <bool F16>
+__global__ __launch_bounds__(256) void maxpool16_pad_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out, int N, int H, int W, int C,
+                                                            int ipad, int opad, int Ho, int Wo) {
+    const int c8n = C / 8, Hp = H + 2 * ipad, Wp = W + 2 * ipad, Hop = Ho + 2 * opad, Wop = Wo + 2 * opad;
+    const long long total = (long long)N * Ho * Wo * c8n;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
+        const int c = 8 * (int)(q % c8n);
+        const long long pq = q / c8n;
+        const int x = (int)(pq % Wo), y = (int)((pq / Wo) % Ho), n_ = (int)(pq / ((long long)Wo * Ho));
+        u16x8 best{0, 0, 0, 0, 0, 0, 0, 0};
+        bool have = false;
+        for (int tap = 0; tap < 9; ++tap) {
+            const int ty = 2 * y - 1 + tap / 3, tx = 2 * x - 1 + tap % 3;
+            if (ty < 0 || ty >= H || tx < 0 || tx >= W) continue;
+            const u16x8 v = *reinterpret_cast<const u16x8*>(in + (((long long)n_ * Hp + ty + ipad) * Wp + tx + ipad) * C + c);
+            if (!have) {
+                best = v;
+                have = true;
+                continue;
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float f = to_f32<F16>(v[e]), b = to_f32<F16>(best[e]);
+                if (f > b || f != f) best[e] = v[e];
+            }
+        }
+        *reinterpret_cast<u16x8*>(out + (((long long)n_ * Hop + y + opad) * Wop + x + opad) * C + c) = best;
+    }
+}
+
+// ---- the mean over the H W pixels of an unpadded frame [N][HW][C] -> fp32 [N][C]: thread = (image, 8 consecutive channels), the pixels added in fp32 in
+// their order and divided once.  No atomics: bit-reproducible.
+template <bool F16>
+__global__ __launch_bounds__(256) void avgpool16_kernel(const unsigned short* __restrict__ in, float* __restrict__ out, int N, int HW, int C) {
+    const int c8n = C / 8;
+    const long long total = (long long)N * c8n;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
+        const int c = 8 * (int)(q % c8n);
+        const long long n_ = q / c8n;
+        const unsigned short* src = in + n_ * HW * C + c;
+        float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int p = 0; p < HW; ++p) {
+            const u16x8 v = *reinterpret_cast<const u16x8*>(src + (long long)p * C);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e] += to_f32<F16>(v[e]);
+        }
+        const float cnt = (float)HW;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) out[n_ * C + c + e] = s[e] / cnt;
+    }
+}
+
+// ---- scipy.spatial.distance.correlation per pair of rows: one 256-thread workgroup per pair, two passes (the means, then the three centred sums), each
+// thread's strided partial sums combined by a shuffle tree within the wave and an LDS tree across the four waves: a fixed order, no atomics.
+__device__ __forceinline__ float cd_block_sum(float v, float* red) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();                                          // (the previous sum's readers are done with `red`)
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void corr_distance_kernel(const float* __restrict__ a, const float* __restrict__ b, int D, float* __restrict__ out) {
+    EEG_LDS_BASE(float, red);                                 // [4]
+    const float* pa = a + (long long)blockIdx.x * D;
+    const float* pb = b + (long long)blockIdx.x * D;
+    const int t = threadIdx.x;
+    float sa = 0.f, sb = 0.f;
+    for (int i = t; i < D; i += 256) {
+        sa += pa[i];
+        sb += pb[i];
+    }
+    const float ma = cd_block_sum(sa, red) / (float)D, mb = cd_block_sum(sb, red) / (float)D;
+    float saa = 0.f, sbb = 0.f, sab = 0.f;
+    for (int i = t; i < D; i += 256) {
+        const float x = pa[i] - ma, y = pb[i] - mb;
+        saa += x * x;
+        sbb += y * y;
+        sab += x * y;
+    }
+    saa = cd_block_sum(saa, red);
+    sbb = cd_block_sum(sbb, red);
+    sab = cd_block_sum(sab, red);
+    if (t == 0) out[blockIdx.x] = 1.f - sab / (sqrtf(saa) * sqrtf(sbb));          // a constant row: 0 / 0 = NaN, as scipy gives
+}
+
+// ---- (N, 3, H, W) planes -> a 3-channel layer's frame [N][H + 2 B][Wf][4]: pixel (y, x) at frame (y + B, x + B) as {c0, c1, c2, 0}; a copy of 16-bit patterns.
+// B = 2 in front of AlexNet's 11 x 11 layer, 3 in front of ResNet's 7 x 7 stem.
+template <int B>
 __global__ __launch_bounds__(256) void pack_nchw16_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ frame, int N, int H, int W, int Wf) {
     const long long hw = (long long)H * W, total = N * hw;
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
@@ -194,19 +315,65 @@ __global__ __launch_bounds__(256) void pack_nchw16_kernel(const unsigned short* 
         const int y = (int)(p / W), xx = (int)(p - (long long)y * W);
         const unsigned short* s = x + n_ * 3 * hw + p;
         const u16x4 v{s[0], s[hw], s[2 * hw], 0};
-        *reinterpret_cast<u16x4*>(frame + ((n_ * (H + 4) + y + 2) * Wf + xx + 2) * 4) = v;
+        *reinterpret_cast<u16x4*>(frame + ((n_ * (H + 2 * B) + y + B) * Wf + xx + B) * 4) = v;
     }
 }
 
 // torchvision AlexNet's five convolutions (torchvision/models/alexnet.py): the only shapes eegclip_convrelu16 takes
 struct mn_layer { int KS, stride, pad, Cin, Cout; };
 static const mn_layer MN_LAYERS[5] = {{11, 4, 2, 3, 64}, {5, 1, 2, 64, 192}, {3, 1, 1, 192, 384}, {3, 1, 1, 384, 256}, {3, 1, 1, 256, 256}};
+static const mn_layer MN_STEM = {7, 2, 3, 3, 64};            // torchvision ResNet's conv1 (torchvision/models/resnet.py)
 
-static int mn_in_width(int Wi) {
-    const int Wo = (Wi + 4 - 11) / 4 + 1;
-    int w = 4 * (Wo - 1) + 16;                               // the last window's k-tile: 16 pixels from its left edge
-    if (w < Wi + 4) w = Wi + 4;
-    return (w + 1) & ~1;                                     // even: every row starts at a 16-byte boundary
+// a 3-channel layer's frame width: at least the image and its border, and the 16 pixels of the last window's k-tile; even, so every row starts at 16 bytes
+static int mn_first_width(int Wi, const mn_layer& L) {
+    const int Wo = (Wi + 2 * L.pad - L.KS) / L.stride + 1;
+    int w = L.stride * (Wo - 1) + 16;
+    if (w < Wi + 2 * L.pad) w = Wi + 2 * L.pad;
+    return (w + 1) & ~1;
+}
+static int mn_in_width(int Wi) { return mn_first_width(Wi, MN_LAYERS[0]); }
+
+// what eegclip_convrelu16 and eegclip_convbn16 share: the tile loop's geometry for a layer (0, or EEGCLIP_EINVAL past the kernel's 32-bit offsets) ..
+static int mn_geometry(mn_args& a, const mn_layer& L, int N, int Hi, int Wi, int out_pad) {
+    const int Ho = (Hi + 2 * L.pad - L.KS) / L.stride + 1, Wo = (Wi + 2 * L.pad - L.KS) / L.stride + 1;
+    const bool first = L.Cin == 3;
+    a.Ho = Ho; a.Wo = Wo;
+    a.Hp = Hi + 2 * L.pad;                                   // (the frame's border IS the layer's padding: every tap of every window is a frame pixel)
+    a.Wp = first ? mn_first_width(Wi, L) : Wi + 2 * L.pad;
+    a.pix = first ? 4 : L.Cin;
+    a.Hop = Ho + 2 * out_pad; a.Wop = Wo + 2 * out_pad; a.opad = out_pad; a.Cout = L.Cout;
+    a.KH = L.KS; a.KW = first ? 1 : L.KS; a.kc = first ? MN_K : L.Cin; a.stride = L.stride;
+    const long long M = (long long)N * Ho * Wo;
+    // (the kernel's element offsets into the input frame are 32-bit)
+    if (M > 0x7fffffffLL || (long long)N * a.Hp * a.Wp * a.pix > 0x7fffffffLL) return EEGCLIP_EINVAL;
+    a.M = (int)M;
+    const int nj = L.Cout % 128 == 0 ? 2 : 1;
+    a.tiles_n = L.Cout / (64 * nj);
+    a.ntiles = a.tiles_n * ((a.M + MN_T - 1) / MN_T);
+    a.chunk = (a.ntiles + 7) / 8;
+    return 0;
+}
+
+// .. and the launch
+template <class ARGS>
+static int mn_launch(const ARGS& a, int dtype, void* stream) {
+    const int nj = a.Cout % 128 == 0 ? 2 : 1;
+    const size_t lds = 2 * (size_t)(MN_A_B + 64 * nj * MN_ROWB);
+    const dim3 grid((unsigned)(8 * a.chunk)), block(512);
+    const bool f16 = dtype == EEGCLIP_DT_F16;
+    if (nj == 2) {
+        if (f16) EEG_LAUNCH((convrelu16_kernel<true, 2, ARGS>), grid, block, lds, stream, a);
+        else     EEG_LAUNCH((convrelu16_kernel<false, 2, ARGS>), grid, block, lds, stream, a);
+    } else {
+        if (f16) EEG_LAUNCH((convrelu16_kernel<true, 1, ARGS>), grid, block, lds, stream, a);
+        else     EEG_LAUNCH((convrelu16_kernel<false, 1, ARGS>), grid, block, lds, stream, a);
+    }
+    return (int)hipGetLastError();
+}
+
+static unsigned mn_grid(long long threads) {
+    const long long g = (threads + 255) / 256;
+    return (unsigned)(g > 16384 ? 16384 : g);
 }
 
 }  // namespace eeg
@@ -222,40 +389,42 @@ extern "C" int eegclip_convrelu16(const eegclip_convrelu16_desc* d, void* stream
     for (const mn_layer& l : MN_LAYERS)
         if (l.KS == d->KS && l.stride == d->stride && l.pad == d->pad && l.Cin == d->Cin && l.Cout == d->Cout) L = &l;
     if (!L || d->Hi + 2 * L->pad < L->KS || d->Wi + 2 * L->pad < L->KS) return EEGCLIP_EINVAL;
-    const int Ho = (d->Hi + 2 * L->pad - L->KS) / L->stride + 1, Wo = (d->Wi + 2 * L->pad - L->KS) / L->stride + 1;
-    const bool first = L->Cin == 3;
     mn_args a;
     a.in = static_cast<const unsigned short*>(d->in);
     a.W = static_cast<const unsigned short*>(d->W);
     a.bias = static_cast<const unsigned short*>(d->bias);
     a.out = static_cast<unsigned short*>(d->out);
-    a.Ho = Ho; a.Wo = Wo;
-    a.Hp = d->Hi + 2 * L->pad;                               // (the frame's border IS the layer's padding: every tap of every window is a frame pixel)
-    a.Wp = first ? mn_in_width(d->Wi) : d->Wi + 2 * L->pad;
-    a.pix = first ? 4 : L->Cin;
-    a.Hop = Ho + 2 * d->out_pad; a.Wop = Wo + 2 * d->out_pad; a.opad = d->out_pad; a.Cout = L->Cout;
-    a.KH = L->KS; a.KW = first ? 1 : L->KS; a.kc = first ? MN_K : L->Cin; a.stride = L->stride;
-    const long long M = (long long)d->N * Ho * Wo;
-    // (the kernel's element offsets into the input frame are 32-bit)
-    if (M > 0x7fffffffLL || (long long)d->N * a.Hp * a.Wp * a.pix > 0x7fffffffLL) return EEGCLIP_EINVAL;
-    a.M = (int)M;
+    if (mn_geometry(a, *L, d->N, d->Hi, d->Wi, d->out_pad)) return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d->in) | reinterpret_cast<uintptr_t>(d->W)) & 15u) return EEGCLIP_EALIGN;
     if ((reinterpret_cast<uintptr_t>(d->out) | reinterpret_cast<uintptr_t>(d->bias)) & 7u) return EEGCLIP_EALIGN;
-    const int nj = L->Cout % 128 == 0 ? 2 : 1;
-    a.tiles_n = L->Cout / (64 * nj);
-    a.ntiles = a.tiles_n * ((a.M + MN_T - 1) / MN_T);
-    a.chunk = (a.ntiles + 7) / 8;
-    const size_t lds = 2 * (size_t)(MN_A_B + 64 * nj * MN_ROWB);
-    const dim3 grid((unsigned)(8 * a.chunk)), block(512);
-    const bool f16 = d->dtype == EEGCLIP_DT_F16;
-    if (nj == 2) {
-        if (f16) EEG_LAUNCH((convrelu16_kernel<true, 2>), grid, block, lds, stream, a);
-        else     EEG_LAUNCH((convrelu16_kernel<false, 2>), grid, block, lds, stream, a);
-    } else {
-        if (f16) EEG_LAUNCH((convrelu16_kernel<true, 1>), grid, block, lds, stream, a);
-        else     EEG_LAUNCH((convrelu16_kernel<false, 1>), grid, block, lds, stream, a);
-    }
-    return (int)hipGetLastError();
+    return mn_launch(a, d->dtype, stream);
+}
+
+extern "C" int eegclip_convbn16_in_width(int Wi) { return Wi < 1 ? EEGCLIP_EINVAL : mn_first_width(Wi, MN_STEM); }
+
+extern "C" int eegclip_convbn16(const eegclip_convbn16_desc* d, void* stream) {
+    if (!d || !d->in || !d->W || !d->scale || !d->shift || !d->out || d->N < 1 || d->Hi < 1 || d->Wi < 1 || d->out_pad < 0 || d->out_pad > 2 ||
+        (d->relu != 0 && d->relu != 1) || !half_dtype_ok(d->dtype))
+        return EEGCLIP_EINVAL;
+    mn_layer L = {d->KS, d->stride, d->pad, d->Cin, d->Cout};
+    const bool stem = L.KS == MN_STEM.KS && L.stride == MN_STEM.stride && L.pad == MN_STEM.pad && L.Cin == MN_STEM.Cin && L.Cout == MN_STEM.Cout;
+    const bool body = (L.KS == 1 || L.KS == 3) && (L.stride == 1 || L.stride == 2) && L.pad == L.KS / 2 && L.Cin >= 64 && L.Cin % 64 == 0 && L.Cout >= 64 &&
+                      L.Cout % 64 == 0;
+    if (!stem && !body) return EEGCLIP_EINVAL;
+    mn_bn_args a;
+    a.in = static_cast<const unsigned short*>(d->in);
+    a.W = static_cast<const unsigned short*>(d->W);
+    a.bias = nullptr;
+    a.out = static_cast<unsigned short*>(d->out);
+    a.scale = static_cast<const float*>(d->scale);
+    a.shift = static_cast<const float*>(d->shift);
+    a.residual = static_cast<const unsigned short*>(d->residual);
+    a.relu = d->relu;
+    if (mn_geometry(a, L, d->N, d->Hi, d->Wi, d->out_pad)) return EEGCLIP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(d->in) | reinterpret_cast<uintptr_t>(d->W)) & 15u) return EEGCLIP_EALIGN;
+    if ((reinterpret_cast<uintptr_t>(d->out) | reinterpret_cast<uintptr_t>(d->residual)) & 7u) return EEGCLIP_EALIGN;
+    if ((reinterpret_cast<uintptr_t>(d->scale) | reinterpret_cast<uintptr_t>(d->shift)) & 3u) return EEGCLIP_EALIGN;
+    return mn_launch(a, d->dtype, stream);
 }
 
 extern "C" int eegclip_maxpool16(const void* in, void* out, int N, int H, int W, int C, int in_pad, int out_pad, int dtype, void* stream) {
@@ -272,12 +441,49 @@ extern "C" int eegclip_maxpool16(const void* in, void* out, int N, int H, int W,
     return (int)hipGetLastError();
 }
 
+extern "C" int eegclip_maxpool16_pad(const void* in, void* out, int N, int H, int W, int C, int in_pad, int out_pad, int dtype, void* stream) {
+    if (!in || !out || N < 1 || H < 1 || W < 1 || C < 8 || C % 8 || in_pad < 0 || in_pad > 2 || out_pad < 0 || out_pad > 2 || !half_dtype_ok(dtype))
+        return EEGCLIP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) return EEGCLIP_EALIGN;
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const dim3 grid(mn_grid((long long)N * Ho * Wo * (C / 8)));
+    const unsigned short* i16 = static_cast<const unsigned short*>(in);
+    unsigned short* o16 = static_cast<unsigned short*>(out);
+    if (dtype == EEGCLIP_DT_F16) EEG_LAUNCH((maxpool16_pad_kernel<true>), grid, dim3(256), 0, stream, i16, o16, N, H, W, C, in_pad, out_pad, Ho, Wo);
+    else                         EEG_LAUNCH((maxpool16_pad_kernel<false>), grid, dim3(256), 0, stream, i16, o16, N, H, W, C, in_pad, out_pad, Ho, Wo);
+    return (int)hipGetLastError();
+}
+
+extern "C" int eegclip_avgpool16(const void* in, float* out, int N, int H, int W, int C, int dtype, void* stream) {
+    if (!in || !out || N < 1 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL || C < 8 || C % 8 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 3u)) return EEGCLIP_EALIGN;
+    const dim3 grid(mn_grid((long long)N * (C / 8)));
+    const unsigned short* i16 = static_cast<const unsigned short*>(in);
+    if (dtype == EEGCLIP_DT_F16) EEG_LAUNCH((avgpool16_kernel<true>), grid, dim3(256), 0, stream, i16, out, N, H * W, C);
+    else                         EEG_LAUNCH((avgpool16_kernel<false>), grid, dim3(256), 0, stream, i16, out, N, H * W, C);
+    return (int)hipGetLastError();
+}
+
+extern "C" int eegclip_corr_distance(const float* a, const float* b, int N, int D, float* out, void* stream) {
+    if (!a || !b || !out || N < 1 || D < 2) return EEGCLIP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out)) & 3u) return EEGCLIP_EALIGN;
+    EEG_LAUNCH(corr_distance_kernel, dim3((unsigned)N), dim3(256), 4 * sizeof(float), stream, a, b, D, out);
+    return (int)hipGetLastError();
+}
+
 extern "C" int eegclip_pack_nchw16(const void* x, void* frame, int N, int H, int W, int dtype, void* stream) {
     if (!x || !frame || N < 1 || H < 7 || W < 7 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(x) & 1u) || (reinterpret_cast<uintptr_t>(frame) & 15u)) return EEGCLIP_EALIGN;
-    long long g = ((long long)N * H * W + 255) / 256;
-    if (g > 16384) g = 16384;
-    EEG_LAUNCH(pack_nchw16_kernel, dim3((unsigned)g), dim3(256), 0, stream, static_cast<const unsigned short*>(x), static_cast<unsigned short*>(frame), N, H, W,
-               mn_in_width(W));
+    EEG_LAUNCH((pack_nchw16_kernel<2>), dim3(mn_grid((long long)N * H * W)), dim3(256), 0, stream, static_cast<const unsigned short*>(x),
+               static_cast<unsigned short*>(frame), N, H, W, mn_in_width(W));
     return (int)hipGetLastError();
 }
+
+extern "C" int eegclip_pack_nchw16_stem(const void* x, void* frame, int N, int H, int W, int dtype, void* stream) {
+    if (!x || !frame || N < 1 || H < 1 || W < 1 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(x) & 1u) || (reinterpret_cast<uintptr_t>(frame) & 15u)) return EEGCLIP_EALIGN;
+    EEG_LAUNCH((pack_nchw16_kernel<3>), dim3(mn_grid((long long)N * H * W)), dim3(256), 0, stream, static_cast<const unsigned short*>(x),
+               static_cast<unsigned short*>(frame), N, H, W, mn_first_width(W, MN_STEM));
+    return (int)hipGetLastError();
+}
+

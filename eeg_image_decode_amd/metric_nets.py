@@ -1,12 +1,20 @@
-"""The feature nets of the reference's metrics table that this package carries: torchvision's AlexNet up to `features.11`, on HIP kernels
-(csrc/metric_nets.hip).  The metrics notebooks under Generation/ (copies of MindEye's Reconstruction_Metrics) take alexnet(weights=IMAGENET1K_V1)
+"""The feature nets of the reference's metrics table that this package carries: torchvision's AlexNet up to `features.11` and a ResNet-50 trunk up to
+`avgpool` (the SwAV row), on HIP kernels (csrc/metric_nets.hip).  The metrics notebooks under Generation/ (copies of MindEye's Reconstruction_Metrics) take alexnet(weights=IMAGENET1K_V1)
 through create_feature_extractor at `features.4` (the AlexNet(2) row) and `features.11` (the AlexNet(5) row) and score both by two-way identification.
 
 AlexNetFeatures is the architecture in torchvision's key layout with seeded random weights, as every model of this package: load the real checkpoint
 with load_state_dict(torchvision.models.alexnet(weights="IMAGENET1K_V1").state_dict()).  One forward of a chunk of images is 8 launches: the NCHW ->
 frame pack, five convolution + bias + ReLU launches and two max-pools; the third pool (`features.12`) and the classifier are never run.  There is no
 eager path.  `lib`, `require_cuda` and `raw_stream` are called as this module's globals (tests/emu_patch.py swaps them).
+
+ResNetFeatures is torchvision's ResNet with Bottleneck blocks (v1.5: the stride sits on conv2) without its `fc`, in torchvision's key layout, which is also
+that of facebookresearch/swav's resnet50 (its ConstantPad2d(1) + padding=2 stem equals padding=3): the notebooks take the SwAV checkpoint at `avgpool` and
+score np.mean of scipy's correlation distance per pair.  swav_resnet50() is the (3, 4, 6, 3) net; load the real file with load_state_dict.  One forward of a
+chunk is 56 launches at full depth: the pack, 53 convolutions whose epilogue carries eval-mode BatchNorm as fp32 scale / shift, the residual add and the
+ReLU (the downsample is a launch of its own without ReLU), one padded max-pool and one average pool -- no elementwise launch and no torch arithmetic between.
 """
+import math
+
 import torch
 from torch import nn
 
@@ -127,3 +135,146 @@ class AlexNetFeatures(nn.Module):
         if deep:
             out["features.11"] = out11.permute(0, 3, 1, 2)
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------- ResNet trunk (the SwAV row)
+WIDTHS = (64, 128, 256, 512)                    # torchvision/models/resnet.py: the bottleneck width of layer1 .. layer4; a block's output is 4 x that
+DROPPED = ("fc.", "projection_head.", "prototypes.")
+MIN_SIDE = 1                                    # every layer pads by KS / 2 and the pools round up: a 1 x 1 image reaches `avgpool` (as 1 x 1 throughout)
+
+
+def pool_pad_out(n):
+    return (n - 1) // 2 + 1
+
+
+class _Bottleneck(nn.Module):
+    """torchvision's Bottleneck as a holder of parameters (never called): conv1 1 x 1, conv2 3 x 3 with the stride, conv3 1 x 1 to 4 x width, a BatchNorm
+    behind each, and in a stage's first block `downsample` = Sequential(1 x 1 convolution with the stride, BatchNorm)"""
+
+    def __init__(self, cin, width, stride, downsample):
+        super().__init__()
+        self.conv1, self.bn1 = nn.Conv2d(cin, width, 1, bias=False), nn.BatchNorm2d(width)
+        self.conv2, self.bn2 = nn.Conv2d(width, width, 3, stride, 1, bias=False), nn.BatchNorm2d(width)
+        self.conv3, self.bn3 = nn.Conv2d(width, 4 * width, 1, bias=False), nn.BatchNorm2d(4 * width)
+        if downsample:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, 4 * width, 1, stride, bias=False), nn.BatchNorm2d(4 * width))
+        self.stride = stride
+
+
+class ResNetFeatures(nn.Module):
+    def __init__(self, layers=(3, 4, 6, 3), dtype=torch.float16, device="cuda", seed=0):
+        super().__init__()
+        if len(layers) != 4 or any(int(n) < 1 for n in layers):
+            raise EegclipError(f"ResNetFeatures takes four stage depths >= 1; got {layers}")
+        self.layers = tuple(int(n) for n in layers)
+        with seeded_parameters(self, dtype, seed=seed):
+            self.conv1, self.bn1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False), nn.BatchNorm2d(64)
+            cin = 64
+            for s, (width, n) in enumerate(zip(WIDTHS, self.layers)):
+                blocks = []
+                for i in range(n):
+                    blocks.append(_Bottleneck(cin, width, (2 if s > 0 and i == 0 else 1), i == 0))
+                    cin = 4 * width
+                setattr(self, f"layer{s + 1}", nn.Sequential(*blocks))
+            # the identity BatchNorm of PyTorch's defaults would let a wrong fold pass: every BatchNorm tensor is drawn away from it
+            for m in self.modules():
+                if isinstance(m, nn.Conv2d):
+                    nn.init.normal_(m.weight, 0.0, math.sqrt(2.0 / (m.in_channels * m.kernel_size[0] * m.kernel_size[1])))
+                elif isinstance(m, nn.BatchNorm2d):
+                    nn.init.uniform_(m.weight, 0.5, 1.25)
+                    nn.init.uniform_(m.bias, -0.25, 0.25)
+                    nn.init.uniform_(m.running_mean, -0.25, 0.25)
+                    nn.init.uniform_(m.running_var, 0.5, 1.5)
+        for m in self.modules():                                  # BatchNorm tensors are fp32 (the seeded values are exact in `dtype`; a checkpoint's keep
+            if isinstance(m, nn.BatchNorm2d):                     # their precision): the kernels take them as fp32 scale / shift
+                m.float()
+        self.to(device)
+        self._packed, self._frames = PackedWeights(), {}
+
+    @property
+    def dtype(self):
+        return self.conv1.weight.dtype
+
+    @property
+    def device(self):
+        return self.conv1.weight.device
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """torchvision's ResNet keys without `fc`; a full torchvision state dict or a SwAV checkpoint loads too: a leading `module.` is stripped and the
+        fc.* / projection_head.* / prototypes.* keys are dropped.  Any other unknown or missing key is an error (strict)."""
+        sd = {}
+        for k, v in state_dict.items():
+            k = k[len("module."):] if k.startswith("module.") else k
+            if not k.startswith(DROPPED):
+                sd[k] = v
+        return super().load_state_dict(sd, strict=strict, **kw)
+
+    def _layer(self, tag, conv, bn):
+        """(packed weight, scale, shift) of a convolution and the BatchNorm behind it: the weight in the kernel's k order -- [Cout][ky][kx][ci]; for the stem
+        [64][ky][64], element 4 kx + ci, the rest zero -- and eval-mode BatchNorm as fp32 vectors, NOT folded into the 16-bit weights"""
+        def make():
+            w = conv.weight.detach().permute(0, 2, 3, 1)          # (Cout, ky, kx, ci)
+            if w.shape[3] == 3:
+                p = torch.zeros(w.shape[0], w.shape[1], 16, 4, dtype=w.dtype, device=w.device)
+                p[:, :, :w.shape[2], :3] = w
+                w = p
+            scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+            shift = bn.bias.detach().float() - bn.running_mean.detach().float() * scale
+            return w.reshape(w.shape[0], -1).contiguous(), scale.contiguous(), shift.contiguous()
+        return self._packed.get(tag, (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), make)
+
+    _frame = AlexNetFeatures._frame
+
+    def _conv(self, tag, conv, bn, src, out, nb, Hi, Wi, out_pad, relu, residual=None):
+        w, scale, shift = self._layer(tag, conv, bn)
+        d = _abi.ConvBn16Desc(in_=src.data_ptr(), W=w.data_ptr(), scale=scale.data_ptr(), shift=shift.data_ptr(),
+                              residual=residual.data_ptr() if residual is not None else None, out=out.data_ptr(), N=nb, Hi=Hi, Wi=Wi,
+                              Cin=conv.in_channels, Cout=conv.out_channels, KS=conv.kernel_size[0], stride=conv.stride[0], pad=conv.padding[0],
+                              out_pad=out_pad, relu=int(relu), dtype=dtype_code(self.dtype))
+        check(lib().eegclip_convbn16(d, raw_stream()), f"convbn16 ({tag}, {nb} x {Hi} x {Wi})")
+
+    def forward(self, x, chunk=64):
+        """x: (B, 3, H, W), normalised (preprocess.swav_preprocess), of this net's dtype and on its device -> (B, 512 * 4) fp32: the `avgpool` node,
+        flattened.  H, W >= MIN_SIDE = 1.  The batch runs `chunk` images at a time through frames that are reused, so only the result grows with B."""
+        require_cuda(x, "x")
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.dtype != self.dtype or x.device != self.device:
+            raise EegclipError(f"ResNetFeatures takes (B, 3, H, W) {self.dtype} on {self.device}; got {tuple(x.shape)} {x.dtype} on {x.device}")
+        B, _, H, W = x.shape
+        if min(H, W) < MIN_SIDE or chunk < 1:
+            raise EegclipError(f"ResNetFeatures needs images of at least {MIN_SIDE} x {MIN_SIDE} and chunk >= 1; got {H} x {W}, chunk {chunk}")
+        x = x.contiguous()
+        L, dt = lib(), dtype_code(self.dtype)
+        out = torch.empty(B, 4 * WIDTHS[3], dtype=torch.float32, device=self.device)
+        wf = L.eegclip_convbn16_in_width(W)
+        h1, w1 = conv_out(H, 7, 2, 3), conv_out(W, 7, 2, 3)
+        for b0 in range(0, B, chunk):
+            nb = min(chunk, B - b0)
+            f0 = self._frame("in", nb, (H + 6, wf, 4))
+            check(L.eegclip_pack_nchw16_stem(x[b0:b0 + nb].data_ptr(), f0.data_ptr(), nb, H, W, dt, raw_stream()), f"pack_nchw16_stem ({nb} x {H} x {W})")
+            a = self._frame("conv1", nb, (h1, w1, 64))
+            self._conv("conv1", self.conv1, self.bn1, f0, a, nb, H, W, 0, True)
+            h, w = pool_pad_out(h1), pool_pad_out(w1)
+            cur = self._frame("pool", nb, (h, w, 64))
+            check(L.eegclip_maxpool16_pad(a.data_ptr(), cur.data_ptr(), nb, h1, w1, 64, 0, 0, dt, raw_stream()), f"maxpool16_pad ({nb} x {h1} x {w1} x 64)")
+            for s, width in enumerate(WIDTHS):
+                for i, blk in enumerate(getattr(self, f"layer{s + 1}")):
+                    tag = f"layer{s + 1}.{i}"
+                    ho, wo = conv_out(h, 3, blk.stride, 1), conv_out(w, 3, blk.stride, 1)
+                    c1 = self._frame(f"layer{s + 1}.c1.{min(i, 1)}", nb, (h + 2, w + 2, width))        # (a border of 1: the 3 x 3 layer reads it)
+                    self._conv(tag + ".conv1", blk.conv1, blk.bn1, cur, c1, nb, h, w, 1, True)
+                    c2 = self._frame(f"layer{s + 1}.c2", nb, (ho, wo, width))
+                    self._conv(tag + ".conv2", blk.conv2, blk.bn2, c1, c2, nb, h, w, 0, True)
+                    res = cur
+                    if i == 0:
+                        res = self._frame(f"layer{s + 1}.ds", nb, (ho, wo, 4 * width))
+                        self._conv(tag + ".downsample", blk.downsample[0], blk.downsample[1], cur, res, nb, h, w, 0, False)
+                    nxt = self._frame(f"layer{s + 1}.out.{i & 1}", nb, (ho, wo, 4 * width))
+                    self._conv(tag + ".conv3", blk.conv3, blk.bn3, c2, nxt, nb, ho, wo, 0, True, residual=res)
+                    cur, h, w = nxt, ho, wo
+            check(L.eegclip_avgpool16(cur.data_ptr(), out[b0:b0 + nb].data_ptr(), nb, h, w, 4 * WIDTHS[3], dt, raw_stream()), f"avgpool16 ({nb} x {h} x {w})")
+        return out
+
+
+def swav_resnet50(**kw):
+    """the ResNet-50 trunk of the metrics table's SwAV row (facebookresearch/swav's resnet50 without its projection head and prototypes), seeded weights"""
+    return ResNetFeatures(layers=(3, 4, 6, 3), **kw)

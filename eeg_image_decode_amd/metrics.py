@@ -6,10 +6,14 @@ Reconstruction_Metrics): PixCorr, SSIM and two-way identification, on images and
 * two_way_identification(real, recon) mean over j of #{ i != j : r[i, j] < r[j, j] } / (N - 1), r = np.corrcoef(real, recon)[:N, N:], for any feature matrices;
 * clip_two_way(images, recons, tower) the same on the `image_embeds` of a CLIP tower of this package;
 * alexnet_two_way(images, recons, net) the AlexNet(2) / AlexNet(5) rows: the same on `features.4` / `features.11` of a metric_nets.AlexNetFeatures;
-* reconstruction_metrics(...)         the table: {"PixCorr", "SSIM"}, the two AlexNet rows when a net is given, and one two-way entry per feature net handed in.
+* correlation_distance(real, recon)   scipy.spatial.distance.correlation of every pair of rows, the score of the notebooks' "distance" rows (EffNet-B, SwAV);
+* swav_distance(images, recons, net)  the SwAV row: the mean of that on the `avgpool` node of a metric_nets.ResNetFeatures (swav_resnet50);
+* reconstruction_metrics(...)         the table: {"PixCorr", "SSIM"}, the two AlexNet rows and the SwAV row when their nets are given, and one two-way entry
+                                      per feature net handed in.
 
-AlexNet's architecture is carried (metric_nets.py, csrc/metric_nets.hip) with seeded weights: load torchvision's IMAGENET1K_V1 state dict into it for the
-notebooks' rows.  The InceptionV3 / EfficientNet-B1 / SwAV rows stay out: hand any callable `images -> features` in as a feature net.
+AlexNet's and the SwAV ResNet-50's architectures are carried (metric_nets.py, csrc/metric_nets.hip) with seeded weights: load torchvision's IMAGENET1K_V1
+state dict / the SwAV checkpoint into them for the notebooks' rows.  The InceptionV3 row stays out: hand any callable `images -> features` in as a feature
+net; the EfficientNet-B1 row is correlation_distance on a net this package does not carry yet.
 
 One difference from the notebooks: they resize with torchvision's Resize(425, BILINEAR) on float tensors; here PIL images, uint8 arrays and float tensors of
 another size go through preprocess.resize_crop_normalize(size, filter="bilinear"), PIL's 8-bit antialiased resize (what Resize does to a PIL image), so the
@@ -129,15 +133,48 @@ def alexnet_two_way(images, recons, net, size=256, return_counts=False):
             for row, node in (("AlexNet(2)", "features.4"), ("AlexNet(5)", "features.11"))}
 
 
-def reconstruction_metrics(images, recons, feature_nets=None, size=425, device=None, alexnet=None):
+def correlation_distance(real_feats, recon_feats):
+    """scipy.spatial.distance.correlation(real[i], recon[i]) for every i: 1 - the Pearson correlation of the two rows -> (N,) fp32 on the device.  Trailing
+    dimensions are flattened; D >= 2 features; a constant row gives NaN, as scipy does.  The notebooks' "distance" rows are np.mean of this."""
+    if not isinstance(real_feats, torch.Tensor) or not isinstance(recon_feats, torch.Tensor):
+        raise EegclipError("correlation_distance takes two feature tensors (N, ...)")
+    if real_feats.shape != recon_feats.shape or real_feats.dim() < 2:
+        raise EegclipError(f"real and reconstruction features are two (N, ...) tensors of one shape; got {tuple(real_feats.shape)} and {tuple(recon_feats.shape)}")
+    g = require_cuda(real_feats, "real_feats").reshape(real_feats.shape[0], -1).float().contiguous()
+    p = require_cuda(recon_feats, "recon_feats").reshape(recon_feats.shape[0], -1).float().contiguous()
+    N, D = g.shape
+    if N < 1 or D < 2 or p.device != g.device:
+        raise EegclipError(f"correlation_distance needs N >= 1 pairs of D >= 2 features on one device; got ({N}, {D}) on {g.device} and {p.device}")
+    out = torch.empty(N, dtype=torch.float32, device=g.device)
+    check(lib().eegclip_corr_distance(g.data_ptr(), p.data_ptr(), N, D, out.data_ptr(), raw_stream()), f"corr_distance ({N} x {D})")
+    return out
+
+
+def swav_distance(images, recons, net, size=224, return_distances=False):
+    """the notebooks' SwAV row: the mean over the pairs of scipy's correlation distance between the `avgpool` features of `net` (a metric_nets.ResNetFeatures;
+    swav_resnet50 with the SwAV checkpoint loaded is the notebooks' net) -- lower is better.  Both sides go through preprocess.swav_preprocess(size), float
+    tensors as values in [0, 1].  return_distances=True: (mean, distances (N,) fp32 on the device)."""
+    feats = []
+    for x in (images, recons):
+        kw = {"in_range": (0.0, 1.0)} if isinstance(x, torch.Tensor) and x.is_floating_point() else {}
+        feats.append(net(preprocess.swav_preprocess(x, size=size, dtype=net.dtype, device=net.device, **kw)))
+    d = correlation_distance(feats[0], feats[1])
+    mean = float(d.mean())
+    return (mean, d) if return_distances else mean
+
+
+def reconstruction_metrics(images, recons, feature_nets=None, size=425, device=None, alexnet=None, swav=None):
     """the notebooks' table for N pairs: {"PixCorr": mean, "SSIM": mean} plus, with alexnet= a metric_nets.AlexNetFeatures, "AlexNet(2)" and "AlexNet(5)"
-    (alexnet_two_way at its default size 256) plus, per `name: callable` of feature_nets, name: the two-way identification score of
-    callable(images) against callable(recons) (each an (N, ...) feature tensor on the device; e.g. lambda x: tower(preprocess.clip_image_processor(x)).image_embeds).
-    The Inception / EffNet / SwAV rows of the notebooks are such callables around nets this package does not carry."""
+    (alexnet_two_way at its default size 256) plus, with swav= a metric_nets.ResNetFeatures, "SwAV" (swav_distance at its default size 224) plus, per
+    `name: callable` of feature_nets, name: the two-way identification score of callable(images) against callable(recons) (each an (N, ...) feature tensor
+    on the device; e.g. lambda x: tower(preprocess.clip_image_processor(x)).image_embeds).  The Inception row of the notebooks is such a callable around a
+    net this package does not carry; the EffNet-B row is correlation_distance on one."""
     pix, ssm = pixcorr_ssim(images, recons, size, device)
     out = {"PixCorr": float(pix.mean()), "SSIM": float(ssm.mean())}
     if alexnet is not None:
         out.update(alexnet_two_way(images, recons, alexnet))
+    if swav is not None:
+        out["SwAV"] = swav_distance(images, recons, swav)
     for name, net in (feature_nets or {}).items():
         if name in out:
             raise EegclipError(f"feature net name {name!r} is taken by another row of the table")

@@ -220,6 +220,12 @@ def alexnet_preprocess(images, size=256, **kw):
     return resize_crop_normalize(images, size, None, "bilinear", IMAGENET_MEAN, IMAGENET_STD, 1 / 255, **kw)
 
 
+def swav_preprocess(images, size=224, **kw):
+    """the metrics notebooks' transform in front of the SwAV ResNet-50: Resize(size, BILINEAR) -- the shortest side becomes `size`, no crop -- and Normalize
+    with ImageNet's mean / std: alexnet_preprocess at the SwAV row's size, with the same note on PIL's 8-bit resize"""
+    return alexnet_preprocess(images, size=size, **kw)
+
+
 def vae_preprocess(images, size=512, filter="bilinear", out_range=(-1, 1), **kw):
     """the low-level script's Resize((size, size)) + ToTensor in front of vae.encode, to out_range: q / 255 * (hi - lo) + lo.  The default (-1, 1) is the range
     diffusers' AutoencoderKL is trained on (VaeImageProcessor.normalize); out_range=(0, 1) is ToTensor alone."""

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 23
+#define EEGCLIP_ABI_VERSION 24
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -1160,6 +1160,48 @@ int eegclip_convrelu16_in_width(int Wi);
 int eegclip_convrelu16(const eegclip_convrelu16_desc* d, void* stream);
 int eegclip_maxpool16(const void* in, void* out, int N, int H, int W, int C, int in_pad, int out_pad, int dtype, void* stream);
 int eegclip_pack_nchw16(const void* x, void* frame, int N, int H, int W, int dtype, void* stream);
+
+/* ---- the feature net of the metrics table's SwAV row (csrc/metric_nets.hip; the reference's metrics notebooks take a ResNet-50 trunk -- torchvision's
+ * v1.5 bottleneck form, torchvision/models/resnet.py:108-164; facebookresearch/swav's src/resnet50.py:1 has the same keys and arithmetic -- at `avgpool` and
+ * score it as np.mean of scipy.spatial.distance.correlation per pair, scipy/spatial/distance.py:577).  (ABI 24.)  Frames, dtypes and reproducibility as above.
+ *   eegclip_convbn16     out[n][y][x][co] = act(scale[co] * conv(in, W)[n][y][x][co] + shift[co] + residual[n][y][x][co]): the tile loop of eegclip_convrelu16
+ *                        (the same kernel template, fp32 accumulation, N tiles of 128 or of 64 where Cout % 128 != 0) with eval-mode BatchNorm as an fp32
+ *                        scale = gamma / sqrt(var + eps) and shift = beta - mean * scale in the epilogue -- the 16-bit weights stay the checkpoint's own values
+ *                        rounded once -- `residual` NULL or a 16-bit frame in the OUTPUT's layout (same out_pad), added in fp32, act = ReLU when relu = 1 and
+ *                        the identity when relu = 0; one 16-bit rounding, at the store.  Takes KS = 1 or 3, stride = 1 or 2, pad = KS / 2, Cin % 64 == 0,
+ *                        Cout % 64 == 0, and the stem (KS, stride, pad, Cin, Cout) = (7, 2, 3, 3, 64); anything else: EEGCLIP_EINVAL.  `in`: the frame
+ *                        [N][Hi + 2 pad][Wi + 2 pad][Cin] (no border in front of a 1 x 1 layer); for the stem the frame eegclip_pack_nchw16_stem writes,
+ *                        [N][Hi + 6][eegclip_convbn16_in_width(Wi)][4].  W: [Cout][KS * KS][Cin]; for the stem [64][7][64] with element 4 kx + ci of row ky,
+ *                        zero where ci = 3 or kx >= 7.  out: [N][Ho + 2 out_pad][Wo + 2 out_pad][Cout], Ho = (Hi + 2 pad - KS) / stride + 1, 0 <= out_pad <= 2.
+ *                        Element offsets into the input frame are 32-bit (EEGCLIP_EINVAL beyond).  EEGCLIP_EALIGN: in / W not 16-byte, out / residual not
+ *                        8-byte, scale / shift not 4-byte aligned.
+ *   eegclip_pack_nchw16_stem  x (N, 3, H, W) planes, 16-bit -> the stem's frame: pixel (y, x) at frame pixel (y + 3, x + 3) as {c0, c1, c2, 0}; the rest of the
+ *                        frame must be zero and is not written.  H, W >= 1.  The stem's k-tile is the 16 frame pixels x 4 channels from a window's left edge:
+ *                        the 9 pixels right of the window and every fourth channel meet zero WEIGHTS, not zero inputs, so an Inf or NaN pixel there makes that
+ *                        window's outputs NaN although a convolution proper would not read it (finite pixels, such as normalised images, are unaffected).
+ *   eegclip_maxpool16_pad  MaxPool2d(3, 2, padding=1) (floor mode), frames as for eegclip_maxpool16, Ho = (H - 1) / 2 + 1, H, W >= 1.  A tap outside the
+ *                        image is skipped, not read as zero: right for negative inputs.  The stored pattern is the largest tap's own; a NaN tap wins.
+ *   eegclip_avgpool16    the unpadded frame [N][H][W][C], C % 8 == 0, 16-byte aligned -> out fp32 [N][C]: the mean over the H W pixels, added in fp32 in
+ *                        their order and divided once (AdaptiveAvgPool2d(1) + flatten).
+ *   eegclip_corr_distance  out[i] = 1 - <a', b'> / (|a'| |b'|), a' = a[i] - mean(a[i]), b' likewise: scipy's correlation distance of row i of a and b, fp32
+ *                        (N, D) dense rows, N >= 1, D >= 2, all three pointers 4-byte aligned.  One workgroup per pair, two passes (means, then the three
+ *                        centred sums), tree reductions in fp32 in a fixed order.  A constant row gives NaN, as scipy does. */
+typedef struct {
+    const void* in;
+    const void* W;
+    const void* scale;
+    const void* shift;
+    const void* residual;
+    void* out;
+    int N, Hi, Wi, Cin, Cout;
+    int KS, stride, pad, out_pad, relu, dtype;
+} eegclip_convbn16_desc;
+int eegclip_convbn16_in_width(int Wi);
+int eegclip_convbn16(const eegclip_convbn16_desc* d, void* stream);
+int eegclip_pack_nchw16_stem(const void* x, void* frame, int N, int H, int W, int dtype, void* stream);
+int eegclip_maxpool16_pad(const void* in, void* out, int N, int H, int W, int C, int in_pad, int out_pad, int dtype, void* stream);
+int eegclip_avgpool16(const void* in, float* out, int N, int H, int W, int C, int dtype, void* stream);
+int eegclip_corr_distance(const float* a, const float* b, int N, int D, float* out, void* stream);
 
 /* ---- per-kernel timing by the kernel's own GPU timestamps (bench.py roofline): eegclip_time_next_launch(start, stop) arms a pair of
  * library-owned events for the FIRST kernel the calling thread's next entry point launches (hipExtLaunchKernel start / stop events: what
