@@ -10,8 +10,8 @@
 // is recomputed per tap from the output pixel (stride 1 or 2; `up`: the source is the nearest-2x upsampled image, i.e. pixel >> 1 -- the Upsample2D +
 // conv pair of the decoder never materialises the upsampled tensor).  Epilogue: + bias, + residual (a tensor shaped like the output).
 // The few layers with 3 / 4 / 8 channels on one side (conv_in, conv_out, quant convs) run on a direct fp32-accumulate kernel, weights in LDS.
-// GroupNorm: one statistics pass (fp64 partial sums per (image, group), atomics onto 64 addresses per image) and one apply pass (+ SiLU) that writes
-// the next convolution's padded operand.
+// GroupNorm: one statistics pass (fp32 sums about a pivot per thread, turned into fp64 partial sums per (image, group), atomics onto 64 addresses per image)
+// and one apply pass (+ SiLU) that writes the next convolution's padded operand.
 #include "half16.h"
 
 #include <stdlib.h>
@@ -253,61 +253,88 @@ __global__ __launch_bounds__(256) void conv_small16_kernel(const cv_args a) {
 constexpr int GN_PB = 256;
 template <bool F16>
 __global__ __launch_bounds__(256) void gn_stats16_kernel(const unsigned short* __restrict__ x, int H, int W, int C, int pad, int groups, double* __restrict__ sums) {
-    EEG_LDS_BASE(float, red);                                // [2][groups]
+    EEG_LDS_BASE(double, part);                              // [256][2 halves](sum x, sum x^2)
     const int n_ = blockIdx.y, t = threadIdx.x, hw = H * W, Wp = W + 2 * pad, Hp = H + 2 * pad;
-    for (int i = t; i < 2 * groups; i += 256) red[i] = 0.f;
-    __syncthreads();
     const int p0 = blockIdx.x * GN_PB, p1 = p0 + GN_PB < hw ? p0 + GN_PB : hw;
     const int cpg = C / groups, c8n = C / 8;
     if ((C & 7) == 0 && c8n <= 256 && 256 % c8n == 0 && (groups & 1) == 0 && groups <= 256 && (reinterpret_cast<uintptr_t>(x) & 15u) == 0) {
         const int cc = t % c8n, pl = t / c8n, ppi = 256 / c8n;
-        float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
+        // sums of (x - k) and (x - k)^2 about a pivot k per half-chunk, the first value read: fp32 sums of x and x^2 lose the variance of a group whose
+        // |mean| is large against its deviation (sum x^2 / n - mean^2 cancels (mean / sd)^2 of their 2^24: an fp16 decode's rstd off by 1 % at mean / sd 160)
+        // (the pivots' read is the loop's own first read, not one more round trip in front of it; a lane without a pixel has k = 0 and counts n = 0)
+        // The even and the odd channels of a half are summed apart, two floats per instruction (v_pk_add_f32 / v_pk_mul_f32): at 512 channels, 128 x 128, one
+        // wave per SIMD, the loop's VALU instructions are the kernel's time
+        f32x2_t s0 = {0.f, 0.f}, q0 = {0.f, 0.f}, s1 = {0.f, 0.f}, q1 = {0.f, 0.f};
+        int cnt = 0;
+        auto load = [&](int p) {
+            const int y = p / W, xx = p - y * W;
+            return *reinterpret_cast<const u16x8*>(x + (((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C + 8 * cc);
+        };
+        u16x8 vk = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (p0 + pl < p1) vk = load(p0 + pl);
+        const float k0 = to_f32<F16>(vk[0]), k1 = to_f32<F16>(vk[4]);
+        const f32x2_t k0v = {k0, k0}, k1v = {k1, k1};
 #pragma unroll 4
         for (int p = p0 + pl; p < p1; p += ppi) {
-            const int y = p / W, xx = p - y * W;
-            const u16x8 v = *reinterpret_cast<const u16x8*>(x + (((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C + 8 * cc);
+            const u16x8 v = load(p);
+            ++cnt;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float a = to_f32<F16>(v[e]), b = to_f32<F16>(v[4 + e]);
+            for (int e = 0; e < 4; e += 2) {
+                const f32x2_t a = f32x2_t{to_f32<F16>(v[e]), to_f32<F16>(v[e + 1])} - k0v, b = f32x2_t{to_f32<F16>(v[4 + e]), to_f32<F16>(v[5 + e])} - k1v;
                 s0 += a; q0 += a * a;
                 s1 += b; q1 += b * b;
             }
         }
-        // fixed-order combine (two decodes of one latent are bit-identical: tests/test_vae_gpu.py): every thread leaves its two half-chunk pairs in LDS, thread g
-        // adds group g's entries -- half-chunks g cpg / 4 .. of every pixel lane -- in index order
-        float* part = red + 2 * groups;                      // [256][4]
-        *reinterpret_cast<f32x4*>(part + 4 * t) = f32x4{s0, q0, s1, q1};
+        // every thread turns its two half-chunks into (sum x, sum x^2) over their n = 4 cnt values in fp64 -- sum x = s + n k, sum x^2 = q + 2 k s + n k^2 -- and
+        // leaves them in LDS; fixed-order combine (two decodes of one latent are bit-identical: tests/test_vae_gpu.py): thread g adds group g's entries --
+        // half-chunks g cpg / 4 .. of every pixel lane -- in index order
+        const double n = 4.0 * cnt, d0 = k0, d1 = k1;
+        const double ds0 = (double)s0[0] + (double)s0[1], ds1 = (double)s1[0] + (double)s1[1];
+        part[4 * t] = ds0 + n * d0;
+        part[4 * t + 1] = (double)q0[0] + (double)q0[1] + 2.0 * d0 * ds0 + n * d0 * d0;
+        part[4 * t + 2] = ds1 + n * d1;
+        part[4 * t + 3] = (double)q1[0] + (double)q1[1] + 2.0 * d1 * ds1 + n * d1 * d1;
         __syncthreads();
         if (t < groups) {
             const int hpg = cpg / 4;                         // 4-channel half-chunks per group
-            float s_ = 0.f, q = 0.f;
+            double S = 0.0, Q = 0.0;
             for (int l = 0; l < ppi; ++l)
                 for (int k = 0; k < hpg; ++k) {
                     const int hc = t * hpg + k;              // half-chunk index along the channels: thread (l, hc >> 1), half hc & 1
-                    const float* e = part + 4 * (l * c8n + (hc >> 1)) + 2 * (hc & 1);
-                    s_ += e[0];
-                    q += e[1];
+                    const double* e = part + 4 * (l * c8n + (hc >> 1)) + 2 * (hc & 1);
+                    S += e[0];
+                    Q += e[1];
                 }
-            red[t] = s_;
-            red[groups + t] = q;
+            atomicAdd(sums + ((long long)n_ * groups + t) * 2, S);
+            atomicAdd(sums + ((long long)n_ * groups + t) * 2 + 1, Q);
         }
     } else {
+        // the same pivot form per channel; the channels of a group meet in LDS as doubles ([2][groups], atomics: no fixed order here), then one fp64 atomic pair
+        // per (workgroup, group) as in the vector form
+        for (int i = t; i < 2 * groups; i += 256) part[i] = 0.0;
+        __syncthreads();
         for (int c = t; c < C; c += 256) {
+            const unsigned short* xc = x + c;
+            auto at = [&](int p) {
+                const int y = p / W, xx = p - y * W;
+                return to_f32<F16>(xc[(((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C]);
+            };
+            const float k = at(p0);
             float s_ = 0.f, q = 0.f;
             for (int p = p0; p < p1; ++p) {
-                const int y = p / W, xx = p - y * W;
-                const float v = to_f32<F16>(x[(((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C + c]);
+                const float v = at(p) - k;
                 s_ += v;
                 q += v * v;
             }
-            atomicAdd(red + c / cpg, s_);
-            atomicAdd(red + groups + c / cpg, q);
+            const double n = p1 - p0, kk = k;
+            atomicAdd(part + c / cpg, (double)s_ + n * kk);
+            atomicAdd(part + groups + c / cpg, (double)q + 2.0 * kk * s_ + n * kk * kk);
         }
-    }
-    __syncthreads();
-    for (int g = t; g < groups; g += 256) {
-        atomicAdd(sums + ((long long)n_ * groups + g) * 2, (double)red[g]);
-        atomicAdd(sums + ((long long)n_ * groups + g) * 2 + 1, (double)red[groups + g]);
+        __syncthreads();
+        for (int g = t; g < groups; g += 256) {
+            atomicAdd(sums + ((long long)n_ * groups + g) * 2, part[g]);
+            atomicAdd(sums + ((long long)n_ * groups + g) * 2 + 1, part[groups + g]);
+        }
     }
 }
 // Statistics for the channel counts the vector form above does not take (the UNet's 320 / 640 / 960 / 1280 / 1920 / 2560 channels in 32 groups: 256 % (C / 8)
@@ -319,41 +346,55 @@ __global__ __launch_bounds__(256) void gn_stats16_kernel(const unsigned short* _
 template <bool F16>
 __global__ __launch_bounds__(256) void gn_stats16_pairs_kernel(const unsigned short* __restrict__ x, int H, int W, int C, int pad, int groups,
                                                                double* __restrict__ sums) {
-    EEG_LDS_BASE(float, part);                               // [ppi * c8n][4 pairs][2]
+    EEG_LDS_BASE(double, part);                              // [ppi * c8n][4 pairs](sum x, sum x^2)
     const int n_ = blockIdx.y, t = threadIdx.x, hw = H * W, Wp = W + 2 * pad, Hp = H + 2 * pad;
     const int p0 = blockIdx.x * GN_PB, p1 = p0 + GN_PB < hw ? p0 + GN_PB : hw;
     const int c8n = C / 8, ppi = c8n < 256 ? 256 / c8n : 1, items = ppi * c8n, ppg = C / groups / 2;
     for (int i = t; i < items; i += 256) {
         const int pl = i / c8n, cc = i - pl * c8n;
-        float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int p = p0 + pl; p < p1; p += ppi) {
+        // (sums about a pivot per pair, the first value the item reads, as in gn_stats16_kernel)
+        f32x2_t s[4], q[4], k[4];                            // (the two channels of a pair side by side: two floats per instruction)
+        int cnt = 0;
+        auto load = [&](int p) {
             const int y = p / W, xx = p - y * W;
-            const u16x8 v = *reinterpret_cast<const u16x8*>(x + (((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C + 8 * cc);
+            return *reinterpret_cast<const u16x8*>(x + (((long long)n_ * Hp + y + pad) * Wp + xx + pad) * C + 8 * cc);
+        };
+        u16x8 vk = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (p0 + pl < p1) vk = load(p0 + pl);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            s[j] = q[j] = f32x2_t{0.f, 0.f};
+            k[j] = f32x2_t{to_f32<F16>(vk[2 * j]), to_f32<F16>(vk[2 * j])};
+        }
+        for (int p = p0 + pl; p < p1; p += ppi) {
+            const u16x8 v = load(p);
+            ++cnt;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float a = to_f32<F16>(v[2 * j]), b = to_f32<F16>(v[2 * j + 1]);
-                s[j] += a + b;
-                q[j] += a * a + b * b;
+                const f32x2_t a = f32x2_t{to_f32<F16>(v[2 * j]), to_f32<F16>(v[2 * j + 1])} - k[j];
+                s[j] += a;
+                q[j] += a * a;
             }
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            part[8 * i + 2 * j] = s[j];
-            part[8 * i + 2 * j + 1] = q[j];
+        for (int j = 0; j < 4; ++j) {                         // (sum x, sum x^2) = (s + n k, q + 2 k s + n k^2) over the pair's n = 2 cnt values, in fp64
+            const double n = 2.0 * cnt, d = k[j][0], ds = (double)s[j][0] + (double)s[j][1];
+            part[8 * i + 2 * j] = ds + n * d;
+            part[8 * i + 2 * j + 1] = (double)q[j][0] + (double)q[j][1] + 2.0 * d * ds + n * d * d;
         }
     }
     __syncthreads();
     for (int g = t; g < groups; g += 256) {
-        float s_ = 0.f, q_ = 0.f;
+        double S = 0.0, Q = 0.0;
         for (int l = 0; l < ppi; ++l)
             for (int k = 0; k < ppg; ++k) {
                 const int pr = g * ppg + k;                  // channel pair index: chunk pr / 4, pair pr % 4 of it
-                const float* e = part + 8 * (l * c8n + (pr >> 2)) + 2 * (pr & 3);
-                s_ += e[0];
-                q_ += e[1];
+                const double* e = part + 8 * (l * c8n + (pr >> 2)) + 2 * (pr & 3);
+                S += e[0];
+                Q += e[1];
             }
-        atomicAdd(sums + ((long long)n_ * groups + g) * 2, (double)s_);
-        atomicAdd(sums + ((long long)n_ * groups + g) * 2 + 1, (double)q_);
+        atomicAdd(sums + ((long long)n_ * groups + g) * 2, S);
+        atomicAdd(sums + ((long long)n_ * groups + g) * 2 + 1, Q);
     }
 }
 
@@ -555,11 +596,19 @@ extern "C" int eegclip_groupnorm16(const void* x, int N, int H, int W, int C, in
     if (e != hipSuccess) return (int)e;
     const dim3 gs((unsigned)((H * W + GN_PB - 1) / GN_PB), (unsigned)N);
     if (pairs) {
-        const size_t lds_p = (size_t)(c8n < 256 ? 256 / c8n : 1) * c8n * 8 * sizeof(float);
+        const size_t lds_p = (size_t)(c8n < 256 ? 256 / c8n : 1) * c8n * 8 * sizeof(double);         // (at most 128 KB)
+#if !defined(EEG_EMU)
+        if (lds_p > 64 * 1024) {                             // C > 8192: more dynamic LDS than the default limit of a launch (csrc/vae_attn.hip)
+            e = f16 ? hipFuncSetAttribute((const void*)gn_stats16_pairs_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p)
+                    : hipFuncSetAttribute((const void*)gn_stats16_pairs_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p);
+            if (e != hipSuccess) return (int)e;
+        }
+#endif
         if (f16) EEG_LAUNCH((gn_stats16_pairs_kernel<true>), gs, dim3(256), lds_p, stream, static_cast<const unsigned short*>(x), H, W, C, pad, groups, sums);
         else     EEG_LAUNCH((gn_stats16_pairs_kernel<false>), gs, dim3(256), lds_p, stream, static_cast<const unsigned short*>(x), H, W, C, pad, groups, sums);
     } else {
-        const size_t lds = (2 * (size_t)groups + 256 * 4) * sizeof(float);
+        // (vector form: [256][4]; walk: [2][groups], N groups <= 4096: at most 64 KB)
+        const size_t lds = (groups <= 512 ? 256 * 4 : 2 * (size_t)groups) * sizeof(double);
         if (f16) EEG_LAUNCH((gn_stats16_kernel<true>), gs, dim3(256), lds, stream, static_cast<const unsigned short*>(x), H, W, C, pad, groups, sums);
         else     EEG_LAUNCH((gn_stats16_kernel<false>), gs, dim3(256), lds, stream, static_cast<const unsigned short*>(x), H, W, C, pad, groups, sums);
     }
