@@ -12,7 +12,8 @@ _LAZY = {"GITCaptioner": "git_caption", "WordPieceDecoder": "git_caption", "capt
          "train_low_level": "low_level", "pixcorr_ssim": "metrics", "pixcorr": "metrics", "ssim": "metrics", "two_way_identification": "metrics",
          "clip_two_way": "metrics", "reconstruction_metrics": "metrics", "alexnet_two_way": "metrics", "AlexNetFeatures": "metric_nets",
          "alexnet_preprocess": "preprocess", "ResNetFeatures": "metric_nets", "swav_resnet50": "metric_nets", "swav_preprocess": "preprocess",
-         "correlation_distance": "metrics", "swav_distance": "metrics"}
+         "correlation_distance": "metrics", "swav_distance": "metrics", "EfficientNetFeatures": "metric_nets", "efficientnet_b1": "metric_nets",
+         "effnet_preprocess": "preprocess", "effnet_distance": "metrics"}
 __all__ = sorted(_LAZY)
 
 

@@ -17,7 +17,12 @@
 // (eegclip_convbn16: eval-mode BatchNorm as fp32 scale / shift, the block's residual added in fp32, ReLU or not) for 1 x 1 and 3 x 3 layers at stride 1 or 2 and
 // the 3-channel 7 x 7 stride-2 stem in the form above (a 3-pixel border, [64][7][64] weights; the 9 pixels right of a window must be finite), with
 // MaxPool2d(3, 2, 1), the average pool to fp32 (N, C) and scipy's correlation distance per pair of feature rows.
-#include "half16.h"
+//
+// The EffNet-B row's EfficientNet-B1 trunk takes its dense layers from a third epilogue of the same kernel (eegclip_convbnact16: scale / shift, then none | ReLU |
+// SiLU in fp32, THEN the residual): the 1 x 1 expansions, projections and head at Cin, Cout % 64 == 0 -- the host pads 16, 24, 40 .. channels with zeros -- and
+// the 3-channel 3 x 3 stride-2 stem in the first-layer form (a 1-pixel border, [64][3][64] weights of which EfficientNet fills 32 rows).  The depthwise layers,
+// the squeeze-and-excitation gate and the gate multiply are csrc/mbconv.hip.
+#include "silu16.h"
 
 namespace eeg {
 
@@ -35,6 +40,7 @@ struct mn_args {
     int KH, KW, kc, stride;            // k-tile kt = ((ky KW + kx) kc + c0) / 64 reads 64 elements from frame pixel (y stride + ky, x stride + kx), element c0
     int M, tiles_n, ntiles, chunk;
     static constexpr bool BN = false;  // the epilogue: bias + ReLU
+    static constexpr bool ACT = false; // (eegclip_convbnact16's epilogue)
 };
 
 // eegclip_convbn16's arguments: the same tile loop with the epilogue act(scale[co] acc + shift[co] + residual).  A type of its own, so the kernel argument
@@ -45,6 +51,16 @@ struct mn_bn_args : mn_args {
     const unsigned short* residual;    // NULL, or a frame in the output's own layout
     int relu;
     static constexpr bool BN = true;
+};
+
+// eegclip_convbnact16's arguments (the EfficientNet row): act(scale[co] acc + shift[co]) + residual, act = 0 none | 1 ReLU | 2 SiLU.  Again a type of its own:
+// the two epilogues above keep their instantiations.
+struct mn_act_args : mn_args {
+    const float* scale;                // [Cout]
+    const float* shift;                // [Cout]
+    const unsigned short* residual;    // NULL, or a frame in the output's own layout
+    int act;
+    static constexpr bool BN = true, ACT = true;
 };
 
 // NJ: 32-column blocks per MFMA wave along N; the N tile is 64 NJ wide
@@ -165,7 +181,20 @@ __global__ __launch_bounds__(512) void convrelu16_kernel(const ARGS a) {
             for (int eq = 0; eq < 4; ++eq) {
                 const int n = n0 + wn * 32 * NJ + 32 * j + 8 * eq + 4 * h;
                 u16x4 o;
-                if constexpr (ARGS::BN) {
+                if constexpr (ARGS::ACT) {
+                    // eval-mode BatchNorm as fp32 scale / shift, the activation in fp32, THEN the residual (MBConv's projection has none of the former, its
+                    // expansion none of the latter), one rounding at the store
+                    u16x4 rv{0, 0, 0, 0};
+                    if (a.residual) rv = *reinterpret_cast<const u16x4*>(a.residual + opix + n);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float v = acc[j][i][4 * eq + e] * a.scale[n + e] + a.shift[n + e];
+                        if (a.act == 2) v = silu_exp2(v);
+                        else if (a.act == 1) v = v < 0.f ? 0.f : v;
+                        if (a.residual) v += to_f32<F16>(rv[e]);
+                        o[e] = to_h<F16>(v);
+                    }
+                } else if constexpr (ARGS::BN) {
                     // eval-mode BatchNorm as fp32 scale / shift, the residual added in fp32, one rounding at the store
                     u16x4 rv{0, 0, 0, 0};
                     if (a.residual) rv = *reinterpret_cast<const u16x4*>(a.residual + opix + n);
@@ -306,7 +335,7 @@ __global__ __launch_bounds__(256) void corr_distance_kernel(const float* __restr
 }
 
 // ---- (N, 3, H, W) planes -> a 3-channel layer's frame [N][H + 2 B][Wf][4]: pixel (y, x) at frame (y + B, x + B) as {c0, c1, c2, 0}; a copy of 16-bit patterns.
-// B = 2 in front of AlexNet's 11 x 11 layer, 3 in front of ResNet's 7 x 7 stem.
+// B = 2 in front of AlexNet's 11 x 11 layer, 3 in front of ResNet's 7 x 7 stem, 1 in front of EfficientNet's 3 x 3 stem.
 template <int B>
 __global__ __launch_bounds__(256) void pack_nchw16_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ frame, int N, int H, int W, int Wf) {
     const long long hw = (long long)H * W, total = N * hw;
@@ -323,6 +352,7 @@ __global__ __launch_bounds__(256) void pack_nchw16_kernel(const unsigned short* 
 struct mn_layer { int KS, stride, pad, Cin, Cout; };
 static const mn_layer MN_LAYERS[5] = {{11, 4, 2, 3, 64}, {5, 1, 2, 64, 192}, {3, 1, 1, 192, 384}, {3, 1, 1, 384, 256}, {3, 1, 1, 256, 256}};
 static const mn_layer MN_STEM = {7, 2, 3, 3, 64};            // torchvision ResNet's conv1 (torchvision/models/resnet.py)
+static const mn_layer MN_EFF_STEM = {3, 2, 1, 3, 64};        // torchvision EfficientNet's features.0 (32 filters; rows 32 .. 63 of the packed weight are zero)
 
 // a 3-channel layer's frame width: at least the image and its border, and the 16 pixels of the last window's k-tile; even, so every row starts at 16 bytes
 static int mn_first_width(int Wi, const mn_layer& L) {
@@ -427,6 +457,38 @@ extern "C" int eegclip_convbn16(const eegclip_convbn16_desc* d, void* stream) {
     return mn_launch(a, d->dtype, stream);
 }
 
+extern "C" int eegclip_convbnact16_in_width(int Wi) { return Wi < 1 ? EEGCLIP_EINVAL : mn_first_width(Wi, MN_EFF_STEM); }
+
+extern "C" int eegclip_convbnact16(const eegclip_convbnact16_desc* d, void* stream) {
+    if (!d || !d->in || !d->W || !d->scale || !d->shift || !d->out || d->N < 1 || d->Hi < 1 || d->Wi < 1 || d->out_pad < 0 || d->out_pad > 2 || d->in_pad < 0 ||
+        d->in_pad > 2 || d->act < 0 || d->act > 2 || !half_dtype_ok(d->dtype))
+        return EEGCLIP_EINVAL;
+    const mn_layer L = {d->KS, d->stride, d->pad, d->Cin, d->Cout};
+    const bool stem = L.KS == MN_EFF_STEM.KS && L.stride == MN_EFF_STEM.stride && L.pad == MN_EFF_STEM.pad && L.Cin == MN_EFF_STEM.Cin &&
+                      L.Cout == MN_EFF_STEM.Cout && d->in_pad == 0;
+    const bool point = L.KS == 1 && L.stride == 1 && L.pad == 0 && L.Cin >= 64 && L.Cin % 64 == 0 && L.Cout >= 64 && L.Cout % 64 == 0;
+    if (!stem && !point) return EEGCLIP_EINVAL;
+    mn_act_args a;
+    a.W = static_cast<const unsigned short*>(d->W);
+    a.bias = nullptr;
+    a.out = static_cast<unsigned short*>(d->out);
+    a.scale = static_cast<const float*>(d->scale);
+    a.shift = static_cast<const float*>(d->shift);
+    a.residual = static_cast<const unsigned short*>(d->residual);
+    a.act = d->act;
+    if (mn_geometry(a, L, d->N, d->Hi, d->Wi, d->out_pad)) return EEGCLIP_EINVAL;
+    // a 1 x 1 layer may read the interior of a frame with a border (the depthwise layer in front of it needed one): the tile loop walks the wider frame from
+    // its pixel (in_pad, in_pad)
+    a.Hp += 2 * d->in_pad;
+    a.Wp += 2 * d->in_pad;
+    if ((long long)d->N * a.Hp * a.Wp * a.pix > 0x7fffffffLL) return EEGCLIP_EINVAL;
+    a.in = static_cast<const unsigned short*>(d->in) + ((long long)d->in_pad * a.Wp + d->in_pad) * a.pix;
+    if ((reinterpret_cast<uintptr_t>(d->in) | reinterpret_cast<uintptr_t>(d->W)) & 15u) return EEGCLIP_EALIGN;
+    if ((reinterpret_cast<uintptr_t>(d->out) | reinterpret_cast<uintptr_t>(d->residual)) & 7u) return EEGCLIP_EALIGN;
+    if ((reinterpret_cast<uintptr_t>(d->scale) | reinterpret_cast<uintptr_t>(d->shift)) & 3u) return EEGCLIP_EALIGN;
+    return mn_launch(a, d->dtype, stream);
+}
+
 extern "C" int eegclip_maxpool16(const void* in, void* out, int N, int H, int W, int C, int in_pad, int out_pad, int dtype, void* stream) {
     if (!in || !out || N < 1 || H < 3 || W < 3 || C < 8 || C % 8 || in_pad < 0 || in_pad > 2 || out_pad < 0 || out_pad > 2 || !half_dtype_ok(dtype))
         return EEGCLIP_EINVAL;
@@ -487,3 +549,10 @@ extern "C" int eegclip_pack_nchw16_stem(const void* x, void* frame, int N, int H
     return (int)hipGetLastError();
 }
 
+extern "C" int eegclip_pack_nchw16_pad1(const void* x, void* frame, int N, int H, int W, int dtype, void* stream) {
+    if (!x || !frame || N < 1 || H < 1 || W < 1 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(x) & 1u) || (reinterpret_cast<uintptr_t>(frame) & 15u)) return EEGCLIP_EALIGN;
+    EEG_LAUNCH((pack_nchw16_kernel<1>), dim3(mn_grid((long long)N * H * W)), dim3(256), 0, stream, static_cast<const unsigned short*>(x),
+               static_cast<unsigned short*>(frame), N, H, W, mn_first_width(W, MN_EFF_STEM));
+    return (int)hipGetLastError();
+}

@@ -1,5 +1,5 @@
-"""The feature nets of the reference's metrics table that this package carries: torchvision's AlexNet up to `features.11` and a ResNet-50 trunk up to
-`avgpool` (the SwAV row), on HIP kernels (csrc/metric_nets.hip).  The metrics notebooks under Generation/ (copies of MindEye's Reconstruction_Metrics) take alexnet(weights=IMAGENET1K_V1)
+"""The feature nets of the reference's metrics table that this package carries: torchvision's AlexNet up to `features.11`, a ResNet-50 trunk up to
+`avgpool` (the SwAV row) and EfficientNet-B1 up to `avgpool` (the EffNet-B row; EfficientNetFeatures below), on HIP kernels (csrc/metric_nets.hip, csrc/mbconv.hip).  The metrics notebooks under Generation/ (copies of MindEye's Reconstruction_Metrics) take alexnet(weights=IMAGENET1K_V1)
 through create_feature_extractor at `features.4` (the AlexNet(2) row) and `features.11` (the AlexNet(5) row) and score both by two-way identification.
 
 AlexNetFeatures is the architecture in torchvision's key layout with seeded random weights, as every model of this package: load the real checkpoint
@@ -278,3 +278,229 @@ class ResNetFeatures(nn.Module):
 def swav_resnet50(**kw):
     """the ResNet-50 trunk of the metrics table's SwAV row (facebookresearch/swav's resnet50 without its projection head and prototypes), seeded weights"""
     return ResNetFeatures(layers=(3, 4, 6, 3), **kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- EfficientNet trunk (the EffNet-B row)
+# torchvision/models/efficientnet.py: (expand ratio, kernel, stride, input channels, output channels) of features.1 .. features.7; B0's depths are
+# (1, 2, 2, 3, 3, 4, 1) and B1's ceil(1.1 x) of them
+EFF_STAGES = ((1, 3, 1, 32, 16), (6, 3, 2, 16, 24), (6, 5, 2, 24, 40), (6, 3, 2, 40, 80), (6, 5, 1, 80, 112), (6, 5, 2, 112, 192), (6, 3, 1, 192, 320))
+EFF_B1_LAYERS = (2, 3, 3, 4, 4, 5, 2)
+EFF_STEM, EFF_HEAD = 32, 1280
+ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2
+
+
+def pad64(c):
+    """the channel count a frame carries for `c` channels: the implicit-GEMM kernel takes multiples of 64; the padded channels are zero everywhere"""
+    return (c + 63) // 64 * 64
+
+
+def _conv_bn(cin, cout, k, stride, groups=1):
+    """torchvision's Conv2dNormActivation as a holder of parameters: `.0` the convolution without bias, `.1` the BatchNorm (the activation has no key)"""
+    return nn.Sequential(nn.Conv2d(cin, cout, k, stride, k // 2, groups=groups, bias=False), nn.BatchNorm2d(cout))
+
+
+class _SqueezeExcitation(nn.Module):
+    def __init__(self, channels, squeeze):
+        super().__init__()
+        self.fc1, self.fc2 = nn.Conv2d(channels, squeeze, 1), nn.Conv2d(squeeze, channels, 1)
+
+
+class _MBConv(nn.Module):
+    """torchvision's MBConv as a holder of parameters (never called): `block` = [1 x 1 expansion unless the ratio is 1,] depthwise k x k with the stride,
+    squeeze-and-excitation with max(1, input channels // 4) hidden units, 1 x 1 projection (no activation); the input is added when the shapes allow"""
+
+    def __init__(self, expand, k, stride, cin, cout):
+        super().__init__()
+        self.expand, self.k, self.stride, self.cin, self.cout, self.cexp = expand, k, stride, cin, cout, cin * expand
+        self.residual = stride == 1 and cin == cout
+        layers = [_conv_bn(cin, self.cexp, 1, 1)] if expand != 1 else []
+        layers += [_conv_bn(self.cexp, self.cexp, k, stride, groups=self.cexp), _SqueezeExcitation(self.cexp, max(1, cin // 4)), _conv_bn(self.cexp, cout, 1, 1)]
+        self.block = nn.Sequential(*layers)
+
+
+class EfficientNetFeatures(nn.Module):
+    """torchvision's EfficientNet (B0 / B1 widths) without its classifier, in torchvision's key layout: the notebooks take efficientnet_b1(weights=DEFAULT) at
+    `avgpool`, flatten to (N, 1280) and score np.mean of scipy's correlation distance per pair.  efficientnet_b1() is the (2, 3, 3, 4, 4, 5, 2) net; load the real
+    checkpoint with load_state_dict(torchvision.models.efficientnet_b1(weights="DEFAULT").state_dict()).
+
+    Channel counts here (16, 24, 40, 80, 112, 144, 240, 672 ..) are not multiples of the convolution kernel's 64: every frame carries pad64(C) channels, the
+    packed weights have zero rows / columns there and scale = shift = 0, so a padded channel is exactly 0 through SiLU (0 sigmoid(0)), the gate multiply and the
+    residual.  One forward of a chunk at full depth is 117 launches: the pack, the stem, per block [the expansion,] the depthwise convolution (BatchNorm, SiLU
+    and the squeeze's pooled sums in its epilogue), the gate, the gate multiply and the projection (which carries the residual), the head and the average
+    pool -- no torch arithmetic between.  There is no eager path."""
+
+    def __init__(self, layers=EFF_B1_LAYERS, dtype=torch.float16, device="cuda", seed=0):
+        super().__init__()
+        if len(layers) != 7 or any(int(n) < 1 for n in layers):
+            raise EegclipError(f"EfficientNetFeatures takes seven stage depths >= 1; got {layers}")
+        self.layers = tuple(int(n) for n in layers)
+        with seeded_parameters(self, dtype, seed=seed):
+            stages = [_conv_bn(3, EFF_STEM, 3, 2)]
+            for (expand, k, stride, cin, cout), n in zip(EFF_STAGES, self.layers):
+                stages.append(nn.Sequential(*[_MBConv(expand, k, stride if i == 0 else 1, cin if i == 0 else cout, cout) for i in range(n)]))
+            stages.append(_conv_bn(EFF_STAGES[-1][4], EFF_HEAD, 1, 1))
+            self.features = nn.Sequential(*stages)
+            # He's draw for the convolutions and BatchNorm away from the identity, as ResNetFeatures; the gates are drawn mostly OPEN (fc2.bias around 2): with
+            # PyTorch's defaults every gate averages 0.5, the signal halves per block and `avgpool` no longer depends on the input
+            for m in self.modules():
+                if isinstance(m, nn.Conv2d):
+                    nn.init.normal_(m.weight, 0.0, math.sqrt(2.0 / (m.in_channels // m.groups * m.kernel_size[0] * m.kernel_size[1])))
+                elif isinstance(m, nn.BatchNorm2d):
+                    nn.init.uniform_(m.weight, 0.5, 1.25)
+                    nn.init.uniform_(m.bias, -0.25, 0.25)
+                    nn.init.uniform_(m.running_mean, -0.25, 0.25)
+                    nn.init.uniform_(m.running_var, 0.5, 1.5)
+            for m in self.modules():
+                if isinstance(m, _SqueezeExcitation):
+                    nn.init.normal_(m.fc1.weight, 0.0, math.sqrt(1.0 / m.fc1.in_channels))
+                    nn.init.normal_(m.fc1.bias, 0.0, 0.5)
+                    nn.init.normal_(m.fc2.weight, 0.0, math.sqrt(4.0 / m.fc2.in_channels))
+                    nn.init.normal_(m.fc2.bias, 2.0, 0.5)
+        for m in self.modules():                                  # BatchNorm tensors are fp32, as in ResNetFeatures
+            if isinstance(m, nn.BatchNorm2d):
+                m.float()
+        self.to(device)
+        self._packed, self._frames = PackedWeights(), {}
+
+    @property
+    def dtype(self):
+        return self.features[0][0].weight.dtype
+
+    @property
+    def device(self):
+        return self.features[0][0].weight.device
+
+    def blocks(self):
+        """[(key prefix, _MBConv)] in the order they run"""
+        return [(f"features.{s}.{i}", blk) for s in range(1, 8) for i, blk in enumerate(self.features[s])]
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """torchvision's EfficientNet keys without `classifier`; a full torchvision state dict loads too: its classifier.* keys are dropped.  Any other unknown
+        or missing key is an error (strict)."""
+        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith("classifier.")}, strict=strict, **kw)
+
+    def _layer(self, tag, conv, bn):
+        """(packed weight, scale, shift) of a dense convolution and the BatchNorm behind it, padded with zeros to pad64 channels: [pad64(Cout)][pad64(Cin)] for
+        a 1 x 1 layer, [64][ky][64] with element 4 kx + ci for the stem (rows 32 .. 63 zero); eval-mode BatchNorm as fp32 vectors, zero in the padding"""
+        def make():
+            w = conv.weight.detach()
+            cout, cin = w.shape[:2]
+            if cin == 3:
+                p = torch.zeros(pad64(cout), w.shape[2], 16, 4, dtype=w.dtype, device=w.device)
+                p[:cout, :, :w.shape[3], :3] = w.permute(0, 2, 3, 1)
+            else:
+                p = torch.zeros(pad64(cout), pad64(cin), dtype=w.dtype, device=w.device)
+                p[:cout, :cin] = w[:, :, 0, 0]
+            return (p.reshape(p.shape[0], -1).contiguous(), *self._scale_shift(bn, pad64(cout)))
+        return self._packed.get(tag, (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), make)
+
+    @staticmethod
+    def _scale_shift(bn, padded):
+        scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+        shift = bn.bias.detach().float() - bn.running_mean.detach().float() * scale
+        out = torch.zeros(2, padded, dtype=torch.float32, device=scale.device)
+        out[0, :scale.numel()], out[1, :scale.numel()] = scale, shift
+        return out[0], out[1]
+
+    def _depthwise(self, tag, conv, bn):
+        """(weight [ky][kx][pad64(C)], scale, shift) of a depthwise convolution and its BatchNorm"""
+        def make():
+            w = conv.weight.detach()                              # (C, 1, k, k)
+            p = torch.zeros(w.shape[2], w.shape[3], pad64(w.shape[0]), dtype=w.dtype, device=w.device)
+            p[:, :, :w.shape[0]] = w[:, 0].permute(1, 2, 0)
+            return (p, *self._scale_shift(bn, pad64(w.shape[0])))
+        return self._packed.get(tag, (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), make)
+
+    def _se(self, tag, se):
+        """(fc1 [sq][pad64(C)], b1 [sq], fc2 [pad64(C)][sq], b2 [pad64(C)]) in the net's dtype, zero in the padding (a padded channel's gate is 0.5, times 0)"""
+        def make():
+            sq, c = se.fc1.weight.shape[:2]
+            w1 = torch.zeros(sq, pad64(c), dtype=self.dtype, device=self.device)
+            w1[:, :c] = se.fc1.weight.detach()[:, :, 0, 0]
+            w2 = torch.zeros(pad64(c), sq, dtype=self.dtype, device=self.device)
+            w2[:c] = se.fc2.weight.detach()[:, :, 0, 0]
+            b2 = torch.zeros(pad64(c), dtype=self.dtype, device=self.device)
+            b2[:c] = se.fc2.bias.detach()
+            return w1, se.fc1.bias.detach().contiguous(), w2, b2
+        return self._packed.get(tag, (se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias), make)
+
+    def _frame(self, role, nb, shape, dtype=None):
+        """a zero-initialised buffer for `nb` images, kept between calls under (role, shape): a frame's border is written by no launch and a role always has
+        the same border, so the interior is simply overwritten"""
+        dtype = dtype or self.dtype
+        f = self._frames.get((role, shape))
+        if f is None or f.shape[0] < nb or f.dtype != dtype or f.device != self.device:
+            f = self._frames[(role, shape)] = torch.zeros((nb, *shape), dtype=dtype, device=self.device)
+        return f[:nb]
+
+    def _conv(self, tag, layer, src, out, nb, Hi, Wi, in_pad, out_pad, act, residual=None):
+        conv, bn = layer[0], layer[1]
+        w, scale, shift = self._layer(tag, conv, bn)
+        stem = conv.in_channels == 3
+        d = _abi.ConvBnAct16Desc(in_=src.data_ptr(), W=w.data_ptr(), scale=scale.data_ptr(), shift=shift.data_ptr(),
+                                 residual=residual.data_ptr() if residual is not None else None, out=out.data_ptr(), N=nb, Hi=Hi, Wi=Wi,
+                                 Cin=3 if stem else pad64(conv.in_channels), Cout=pad64(conv.out_channels), KS=conv.kernel_size[0], stride=conv.stride[0],
+                                 pad=conv.padding[0], in_pad=in_pad, out_pad=out_pad, act=act, dtype=dtype_code(self.dtype))
+        check(lib().eegclip_convbnact16(d, raw_stream()), f"convbnact16 ({tag}, {nb} x {Hi} x {Wi})")
+
+    def forward(self, x, chunk=64):
+        """x: (B, 3, H, W), normalised (preprocess.effnet_preprocess), of this net's dtype and on its device -> (B, 1280) fp32: the `avgpool` node, flattened.
+        H, W >= MIN_SIDE = 1.  The batch runs `chunk` images at a time through frames that are reused, so only the result grows with B."""
+        require_cuda(x, "x")
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.dtype != self.dtype or x.device != self.device:
+            raise EegclipError(f"EfficientNetFeatures takes (B, 3, H, W) {self.dtype} on {self.device}; got {tuple(x.shape)} {x.dtype} on {x.device}")
+        B, _, H, W = x.shape
+        if min(H, W) < MIN_SIDE or chunk < 1:
+            raise EegclipError(f"EfficientNetFeatures needs images of at least {MIN_SIDE} x {MIN_SIDE} and chunk >= 1; got {H} x {W}, chunk {chunk}")
+        x = x.contiguous()
+        L, dt = lib(), dtype_code(self.dtype)
+        out = torch.empty(B, EFF_HEAD, dtype=torch.float32, device=self.device)
+        wf = L.eegclip_convbnact16_in_width(W)
+        h0, w0 = conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1)
+        blocks = self.blocks()
+        for b0 in range(0, B, chunk):
+            nb = min(chunk, B - b0)
+            f0 = self._frame("in", nb, (H + 2, wf, 4))
+            check(L.eegclip_pack_nchw16_pad1(x[b0:b0 + nb].data_ptr(), f0.data_ptr(), nb, H, W, dt, raw_stream()), f"pack_nchw16_pad1 ({nb} x {H} x {W})")
+            # a frame's border is what its READER pads by: the first block has no expansion, so its depthwise layer reads the stem's output itself
+            cur_pad = blocks[0][1].k // 2 if blocks[0][1].expand == 1 else 0
+            cur = self._frame("stem", nb, (h0 + 2 * cur_pad, w0 + 2 * cur_pad, pad64(EFF_STEM)))
+            self._conv("features.0", self.features[0], f0, cur, nb, H, W, 0, cur_pad, ACT_SILU)
+            h, w = h0, w0
+            for idx, (tag, blk) in enumerate(blocks):
+                p, ce = blk.k // 2, pad64(blk.cexp)
+                ho, wo = conv_out(h, blk.k, blk.stride, p), conv_out(w, blk.k, blk.stride, p)
+                if blk.expand != 1:
+                    src = self._frame(f"expand.pad{p}", nb, (h + 2 * p, w + 2 * p, ce))
+                    self._conv(tag + ".block.0", blk.block[0], cur, src, nb, h, w, cur_pad, p, ACT_SILU)
+                elif cur_pad == p:
+                    src = cur
+                else:
+                    raise EegclipError(f"{tag}: a block without expansion reads its input frame's border ({p}); the frame has {cur_pad}")
+                dwl, se = blk.block[-3], blk.block[-2]
+                dw_w, dw_scale, dw_shift = self._depthwise(tag + ".depthwise", dwl[0], dwl[1])
+                S = L.eegclip_dwconv16_slabs(h, w, blk.k, blk.stride)
+                y = self._frame("depthwise", nb, (ho, wo, ce))
+                slab, gate = self._frame("slab", nb, (S, ce), torch.float32), self._frame("gate", nb, (ce,), torch.float32)
+                check(L.eegclip_dwconv16(src.data_ptr(), dw_w.data_ptr(), dw_scale.data_ptr(), dw_shift.data_ptr(), y.data_ptr(), slab.data_ptr(), nb, h, w, ce, blk.k,
+                                         blk.stride, dt, raw_stream()), f"dwconv16 ({tag}, {nb} x {h} x {w} x {ce})")
+                w1, b1, w2, b2 = self._se(tag + ".se", se)
+                check(L.eegclip_se_gate16(slab.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), gate.data_ptr(), nb, S, ho * wo, ce,
+                                          w1.shape[0], dt, raw_stream()), f"se_gate16 ({tag}, {nb} x {ce})")
+                check(L.eegclip_gate_mul16(y.data_ptr(), gate.data_ptr(), nb, ho * wo, ce, dt, raw_stream()), f"gate_mul16 ({tag}, {nb} x {ho} x {wo} x {ce})")
+                # the output frame: the residual is read in the output's own layout, so a block that adds its input keeps the input's border; otherwise the
+                # border the next reader needs (a following block without expansion; a 1 x 1 layer skips whatever border it meets)
+                nxt = blocks[idx + 1][1] if idx + 1 < len(blocks) else None
+                out_pad = cur_pad if blk.residual else (nxt.k // 2 if nxt is not None and nxt.expand == 1 else 0)
+                o = self._frame(f"out{idx & 1}.pad{out_pad}", nb, (ho + 2 * out_pad, wo + 2 * out_pad, pad64(blk.cout)))
+                self._conv(tag + ".block.project", blk.block[-1], y, o, nb, ho, wo, 0, out_pad, ACT_NONE, residual=cur if blk.residual else None)
+                cur, cur_pad, h, w = o, out_pad, ho, wo
+            head = self._frame("head", nb, (h, w, EFF_HEAD))
+            self._conv("features.8", self.features[8], cur, head, nb, h, w, cur_pad, 0, ACT_SILU)
+            check(L.eegclip_avgpool16(head.data_ptr(), out[b0:b0 + nb].data_ptr(), nb, h, w, EFF_HEAD, dt, raw_stream()), f"avgpool16 ({nb} x {h} x {w})")
+        return out
+
+
+def efficientnet_b1(**kw):
+    """the EfficientNet-B1 trunk of the metrics table's EffNet-B row (torchvision's efficientnet_b1 without its classifier), seeded weights"""
+    return EfficientNetFeatures(layers=EFF_B1_LAYERS, **kw)

@@ -232,3 +232,9 @@ def vae_preprocess(images, size=512, filter="bilinear", out_range=(-1, 1), **kw)
     lo, hi = float(out_range[0]), float(out_range[1])
     scale, shift = np.full(3, (hi - lo) / 255.0, np.float64).astype(np.float32), np.full(3, lo, np.float64).astype(np.float32)
     return _run(images, (size, size), None, filter, scale, shift, kw.pop("dtype", torch.float32), kw.pop("device", None), "torchvision", kw.pop("in_range", None), **kw)
+
+
+def effnet_preprocess(images, size=255, **kw):
+    """the metrics notebooks' transform in front of EfficientNet-B1: Resize(255, BILINEAR) -- the shortest side becomes `size`, no crop -- and Normalize with
+    ImageNet's mean / std: alexnet_preprocess at the EffNet-B row's size, with the same note on PIL's 8-bit resize"""
+    return alexnet_preprocess(images, size=size, **kw)

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 24
+#define EEGCLIP_ABI_VERSION 25
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -1202,6 +1202,56 @@ int eegclip_pack_nchw16_stem(const void* x, void* frame, int N, int H, int W, in
 int eegclip_maxpool16_pad(const void* in, void* out, int N, int H, int W, int C, int in_pad, int out_pad, int dtype, void* stream);
 int eegclip_avgpool16(const void* in, float* out, int N, int H, int W, int C, int dtype, void* stream);
 int eegclip_corr_distance(const float* a, const float* b, int N, int D, float* out, void* stream);
+
+/* ---- the feature net of the metrics table's EffNet-B row (csrc/metric_nets.hip, csrc/mbconv.hip; the reference's metrics notebooks take torchvision's
+ * efficientnet_b1 -- torchvision/models/efficientnet.py: MBConv = 1 x 1 expansion, depthwise k x k, squeeze-and-excitation, 1 x 1 projection -- at `avgpool`
+ * and score it as the SwAV row).  (ABI 25.)  Frames, dtypes and reproducibility as above.  Channel counts that are not multiples of 64 are the HOST's business:
+ * it pads frames, weight rows, scale and shift with zeros, and a padded channel then stays exactly 0 through SiLU, the gate multiply and the residual.
+ *   eegclip_convbnact16  out = act(scale[co] * conv(in, W) + shift[co]) + residual: eegclip_convbn16's tile loop (a third instantiation of the same kernel
+ *                        template) with act = 0 (none) | 1 (ReLU) | 2 (SiLU, x / (1 + 2^(-x log2 e)) in fp32) applied BEFORE the residual is added; one 16-bit
+ *                        rounding, at the store.  Takes KS = 1, stride = 1, pad = 0 with Cin % 64 == 0 and Cout % 64 == 0, where `in` is the frame
+ *                        [N][Hi + 2 in_pad][Wi + 2 in_pad][Cin] of which only the interior is read (0 <= in_pad <= 2: the frame may carry the border a
+ *                        depthwise layer needed); and the stem (KS, stride, pad, Cin, Cout) = (3, 2, 1, 3, 64) with in_pad = 0, where `in` is the frame
+ *                        eegclip_pack_nchw16_pad1 writes, [N][Hi + 2][eegclip_convbnact16_in_width(Wi)][4], and W is [64][3][64] with element 4 kx + ci of row
+ *                        ky, zero where ci = 3 or kx >= 3 (EfficientNet's 32 filters are rows 0 .. 31; the host zeroes the rest).  Anything else:
+ *                        EEGCLIP_EINVAL.  out, residual, alignment and the 32-bit offsets as for eegclip_convbn16.
+ *   eegclip_pack_nchw16_pad1  eegclip_pack_nchw16_stem with a border of 1: pixel (y, x) at frame pixel (y + 1, x + 1); the 13 pixels right of a window must
+ *                        be finite.
+ *   eegclip_dwconv16     out[n][y][x][c] = silu(scale[c] * sum_{ky,kx} in[n][y * stride + ky][x * stride + kx][c] W[ky][kx][c] + shift[c]): depthwise
+ *                        convolution + eval-mode BatchNorm + SiLU for k = 3 or 5, stride = 1 or 2, pad = k / 2, C % 8 == 0.  `in`: the frame
+ *                        [N][H + 2 pad][W + 2 pad][C] whose zero border is read, not tested for; out: the UNPADDED frame [N][Ho][Wo][C],
+ *                        Ho = (H + 2 pad - k) / stride + 1; W: 16-bit [k][k][C]; scale, shift: fp32 [C].  fp32 accumulation over the k^2 taps in (ky, kx)
+ *                        order, one rounding at the store.  A thread owns 8 consecutive channels and 4 consecutive output pixels of a row; a workgroup 64
+ *                        channels and 32 such runs, counted along the image's rows.  The same launch writes pooled[n][s][c], fp32
+ *                        [N][eegclip_dwconv16_slabs(H, W, k, stride)][C]: the sum over workgroup s's pixels of the values AS STORED (after the 16-bit rounding),
+ *                        added in a fixed order; every element of `pooled` is written (no memset, no atomics).  EEGCLIP_EINVAL: other k / stride / C, N > 65535,
+ *                        a NULL pointer; EEGCLIP_EALIGN: in / W / out / scale / shift not 16-byte, pooled not 4-byte aligned.
+ *   eegclip_dwconv16_slabs  S of the above: ceil(Ho * ceil(Wo / 4) / 32); EEGCLIP_EINVAL for sizes eegclip_dwconv16 refuses.
+ *   eegclip_se_gate16    gate[n][c] = sigmoid(b2[c] + sum_j W2[c][j] silu(b1[j] + sum_c' W1[j][c'] mean[n][c'])), mean[n][c] = (sum_s pooled[n][s][c]) / HW in a
+ *                        fixed order (increasing s; for C <= 128, 256 / max(64, C rounded up to 64) contiguous runs of s first): squeeze-and-excitation from eegclip_dwconv16's slabs, one workgroup per image.  W1 [sq][C], b1 [sq], W2 [C][sq],
+ *                        b2 [C] are 16-bit, sums and activations fp32 (libm's expf), gate fp32 [N][C].  1 <= C <= 8192, 1 <= sq <= 4096, S >= 1, HW >= 1.
+ *                        EEGCLIP_EALIGN: pooled / gate not 4-byte, a 16-bit pointer not 2-byte aligned.
+ *   eegclip_gate_mul16   y[n][p][c] = round(y[n][p][c] * gate[n][c]) in place on the unpadded frame [N][HW][C], C % 8 == 0: the product in fp32, one
+ *                        rounding; 16-byte accesses (y and gate 16-byte aligned). */
+typedef struct {
+    const void* in;
+    const void* W;
+    const void* scale;
+    const void* shift;
+    const void* residual;
+    void* out;
+    int N, Hi, Wi, Cin, Cout;
+    int KS, stride, pad, in_pad, out_pad, act, dtype;
+} eegclip_convbnact16_desc;
+int eegclip_convbnact16_in_width(int Wi);
+int eegclip_convbnact16(const eegclip_convbnact16_desc* d, void* stream);
+int eegclip_pack_nchw16_pad1(const void* x, void* frame, int N, int H, int W, int dtype, void* stream);
+int eegclip_dwconv16_slabs(int H, int W, int k, int stride);
+int eegclip_dwconv16(const void* in, const void* W, const float* scale, const float* shift, void* out, float* pooled, int N, int H, int Wi, int C, int k,
+                     int stride, int dtype, void* stream);
+int eegclip_se_gate16(const float* pooled, const void* W1, const void* b1, const void* W2, const void* b2, float* gate, int N, int S, int HW, int C, int sq,
+                      int dtype, void* stream);
+int eegclip_gate_mul16(void* y, const float* gate, int N, int HW, int C, int dtype, void* stream);
 
 /* ---- per-kernel timing by the kernel's own GPU timestamps (bench.py roofline): eegclip_time_next_launch(start, stop) arms a pair of
  * library-owned events for the FIRST kernel the calling thread's next entry point launches (hipExtLaunchKernel start / stop events: what
