@@ -13,7 +13,8 @@ _LAZY = {"GITCaptioner": "git_caption", "WordPieceDecoder": "git_caption", "capt
          "clip_two_way": "metrics", "reconstruction_metrics": "metrics", "alexnet_two_way": "metrics", "AlexNetFeatures": "metric_nets",
          "alexnet_preprocess": "preprocess", "ResNetFeatures": "metric_nets", "swav_resnet50": "metric_nets", "swav_preprocess": "preprocess",
          "correlation_distance": "metrics", "swav_distance": "metrics", "EfficientNetFeatures": "metric_nets", "efficientnet_b1": "metric_nets",
-         "effnet_preprocess": "preprocess", "effnet_distance": "metrics"}
+         "effnet_preprocess": "preprocess", "effnet_distance": "metrics", "InceptionFeatures": "metric_nets", "inception_v3": "metric_nets",
+         "inception_preprocess": "preprocess", "inception_two_way": "metrics"}
 __all__ = sorted(_LAZY)
 
 

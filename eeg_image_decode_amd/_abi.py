@@ -118,6 +118,14 @@ class ConvBnAct16Desc(C.Structure):
                 ("KS", C.c_int), ("stride", C.c_int), ("pad", C.c_int), ("in_pad", C.c_int), ("out_pad", C.c_int), ("act", C.c_int), ("dtype", C.c_int)]
 
 
+class ConvBnCat16Desc(C.Structure):
+    _c_name_ = "eegclip_convbncat16_desc"
+    _fields_ = [("in_", C.c_void_p), ("W", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p), ("out", C.c_void_p),
+                ("N", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
+                ("KH", C.c_int), ("KW", C.c_int), ("stride", C.c_int), ("pad_h", C.c_int), ("pad_w", C.c_int), ("in_pad", C.c_int),
+                ("out_pad", C.c_int), ("out_stride", C.c_int), ("out_c0", C.c_int), ("relu", C.c_int), ("dtype", C.c_int)]
+
+
 class Convt16Desc(C.Structure):
     _c_name_ = "eegclip_convt16_desc"
     _fields_ = [("in_", C.c_void_p), ("W", C.c_void_p), ("out", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
@@ -197,7 +205,7 @@ class PlanOp(C.Structure):
 
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_GELU_GRAD = 0, 1, 2, 3
 PREC_F32, PREC_BF16X3 = 0, 1
-ABI_VERSION = 25
+ABI_VERSION = 26
 DT_BF16, DT_F16, DT_F32 = 0, 1, 2
 SRC_U8_HWC, RESIZE_BILINEAR, RESIZE_BICUBIC = 3, 2, 3
 SSIM_TILE_H, SSIM_TILE_W = 32, 32

@@ -22,6 +22,12 @@
 // SiLU in fp32, THEN the residual): the 1 x 1 expansions, projections and head at Cin, Cout % 64 == 0 -- the host pads 16, 24, 40 .. channels with zeros -- and
 // the 3-channel 3 x 3 stride-2 stem in the first-layer form (a 1-pixel border, [64][3][64] weights of which EfficientNet fills 32 rows).  The depthwise layers,
 // the squeeze-and-excitation gate and the gate multiply are csrc/mbconv.hip.
+//
+// The Inception row's InceptionV3 trunk (torchvision's Inception3 up to `avgpool`) is a fourth epilogue (eegclip_convbncat16: scale / shift / ReLU written into
+// channels oc0 .. oc0 + Cout - 1 of a frame with `ostride` channels per pixel): a block's branches write their slices of ONE output frame, so nothing is
+// concatenated.  The tile loop is the same -- it walks KH and KW separately, so 1 x 7, 7 x 1, 1 x 3 and 3 x 1 layers and per-axis padding are host geometry: the
+// frame walk starts at pixel (in_pad - pad_h, in_pad - pad_w) -- and the N tiles cover pad64(Cout) weight rows, of which the epilogue stores the groups below Cout.
+// With it: the 3 x 3 stride-1 average pool of every block, MaxPool2d(3, 2) as a branch of a concatenation, and the pack with transform_input's affine.
 #include "silu16.h"
 
 namespace eeg {
@@ -41,6 +47,7 @@ struct mn_args {
     int M, tiles_n, ntiles, chunk;
     static constexpr bool BN = false;  // the epilogue: bias + ReLU
     static constexpr bool ACT = false; // (eegclip_convbnact16's epilogue)
+    static constexpr bool CAT = false; // (eegclip_convbncat16's epilogue)
 };
 
 // eegclip_convbn16's arguments: the same tile loop with the epilogue act(scale[co] acc + shift[co] + residual).  A type of its own, so the kernel argument
@@ -61,6 +68,16 @@ struct mn_act_args : mn_args {
     const unsigned short* residual;    // NULL, or a frame in the output's own layout
     int act;
     static constexpr bool BN = true, ACT = true;
+};
+
+// eegclip_convbncat16's arguments (the Inception row): relu?(scale[co] acc + shift[co]) written into channels oc0 .. oc0 + Cout - 1 of a frame whose pixels are
+// `ostride` elements apart -- one branch's slice of a block's concatenated output.  `Cout` is the layer's own count (a multiple of 8); the N tiles cover
+// pad64(Cout) weight rows and the epilogue skips the store groups at or past Cout.  A type of its own once more: the three epilogues above keep theirs.
+struct mn_cat_args : mn_args {
+    const float* scale;                // [pad64(Cout)]
+    const float* shift;                // [pad64(Cout)]
+    int relu, ostride, oc0;
+    static constexpr bool BN = true, CAT = true;
 };
 
 // NJ: 32-column blocks per MFMA wave along N; the N tile is 64 NJ wide
@@ -174,14 +191,25 @@ __global__ __launch_bounds__(512) void convrelu16_kernel(const ARGS a) {
         const int m = m0 + wm * 64 + 32 * i + r32;
         if (m >= a.M) continue;
         const int n_ = m / hw, rem = m - n_ * hw, y = rem / a.Wo, x = rem - y * a.Wo;
-        const long long opix = (((long long)n_ * a.Hop + y + a.opad) * a.Wop + x + a.opad) * a.Cout;
+        long long opix = ((long long)n_ * a.Hop + y + a.opad) * a.Wop + x + a.opad;
+        if constexpr (ARGS::CAT) opix = opix * a.ostride + a.oc0;
+        else opix *= a.Cout;
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int eq = 0; eq < 4; ++eq) {
                 const int n = n0 + wn * 32 * NJ + 32 * j + 8 * eq + 4 * h;
                 u16x4 o;
-                if constexpr (ARGS::ACT) {
+                if constexpr (ARGS::CAT) {
+                    // the slice's mask: Cout % 8 == 0, so the two 4-channel groups of an 8-channel run (h = 0, 1) are inside or outside together and the
+                    // test is the same in every lane of the wave; nothing outside the slice is stored
+                    if (n - 4 * h >= a.Cout) continue;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float v = acc[j][i][4 * eq + e] * a.scale[n + e] + a.shift[n + e];
+                        o[e] = to_h<F16>(a.relu && v < 0.f ? 0.f : v);
+                    }
+                } else if constexpr (ARGS::ACT) {
                     // eval-mode BatchNorm as fp32 scale / shift, the activation in fp32, THEN the residual (MBConv's projection has none of the former, its
                     // expansion none of the latter), one rounding at the store
                     u16x4 rv{0, 0, 0, 0};
@@ -240,6 +268,59 @@ __global__ __launch_bounds__(256) void maxpool16_kernel(const unsigned short* __
             }
         }
         *reinterpret_cast<u16x8*>(out + (((long long)n_ * Hop + y + opad) * Wop + x + opad) * C + c) = best;
+    }
+}
+
+// ---- the same pool as a BRANCH of a concatenation (Inception's Mixed_6a / Mixed_7a): it reads the first C channels of a frame whose
+// pixels are `istride` elements apart and writes channels oc0 .. oc0 + C - 1 of the interior of a frame with `ostride` elements per pixel.  Nothing else is written.
+template <bool F16>
+__global__ __launch_bounds__(256) void maxpool16_cat_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out, int N, int H, int W, int C,
+                                                            int istride, int ipad, int ostride, int oc0, int opad, int Ho, int Wo) {
+    const int c8n = C / 8, Hp = H + 2 * ipad, Wp = W + 2 * ipad, Hop = Ho + 2 * opad, Wop = Wo + 2 * opad;
+    const long long total = (long long)N * Ho * Wo * c8n;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
+        const int c = 8 * (int)(q % c8n);
+        const long long pq = q / c8n;
+        const int x = (int)(pq % Wo), y = (int)((pq / Wo) % Ho), n_ = (int)(pq / ((long long)Wo * Ho));
+        const unsigned short* src = in + (((long long)n_ * Hp + 2 * y + ipad) * Wp + 2 * x + ipad) * istride + c;
+        u16x8 best = *reinterpret_cast<const u16x8*>(src);
+#pragma unroll
+        for (int tap = 1; tap < 9; ++tap) {
+            const u16x8 v = *reinterpret_cast<const u16x8*>(src + ((long long)(tap / 3) * Wp + tap % 3) * istride);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float f = to_f32<F16>(v[e]), b = to_f32<F16>(best[e]);
+                if (f > b || f != f) best[e] = v[e];
+            }
+        }
+        *reinterpret_cast<u16x8*>(out + (((long long)n_ * Hop + y + opad) * Wop + x + opad) * ostride + oc0 + c) = best;
+    }
+}
+
+// ---- F.avg_pool2d(x, 3, 1, 1) with count_include_pad=True (the pooled branch of every Inception block): the frame's zero border (ipad >= 1) is read, not
+// tested for; the nine taps are added in fp32 in (ky, kx) order and divided by 9, one rounding at the store into the UNPADDED frame [N][H][W][C].
+// thread = (pixel, 8 consecutive channels), 16-byte accesses.
+template <bool F16>
+__global__ __launch_bounds__(256) void avgpool3x3_16_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out, int N, int H, int W, int C,
+                                                            int ipad) {
+    const int c8n = C / 8, Hp = H + 2 * ipad, Wp = W + 2 * ipad;
+    const long long total = (long long)N * H * W * c8n;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
+        const int c = 8 * (int)(q % c8n);
+        const long long pq = q / c8n;
+        const int x = (int)(pq % W), y = (int)((pq / W) % H), n_ = (int)(pq / ((long long)W * H));
+        const unsigned short* src = in + (((long long)n_ * Hp + y + ipad - 1) * Wp + x + ipad - 1) * C + c;
+        float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const u16x8 v = *reinterpret_cast<const u16x8*>(src + ((long long)(tap / 3) * Wp + tap % 3) * C);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e] += to_f32<F16>(v[e]);
+        }
+        u16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = to_h<F16>(s[e] / 9.f);
+        *reinterpret_cast<u16x8*>(out + pq * C + c) = o;
     }
 }
 
@@ -348,6 +429,25 @@ __global__ __launch_bounds__(256) void pack_nchw16_kernel(const unsigned short* 
     }
 }
 
+// ---- the same pack with a per-channel affine a_c x_c + b_c in front (torchvision Inception3's transform_input) into a frame WITHOUT a border: the product and
+// the sum in fp32, one rounding.  A channel with a_c = 1 and b_c = 0 is copied as a pattern (-0 and NaN payloads included), so the identity is the plain pack.
+template <bool F16>
+__global__ __launch_bounds__(256) void pack_nchw16_affine_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ frame,
+                                                                 const float* __restrict__ a, const float* __restrict__ b, int N, int H, int W, int Wf) {
+    const long long hw = (long long)H * W, total = N * hw;
+    const float av[3] = {a[0], a[1], a[2]}, bv[3] = {b[0], b[1], b[2]};
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
+        const long long n_ = q / hw, p = q - n_ * hw;
+        const int y = (int)(p / W), xx = (int)(p - (long long)y * W);
+        const unsigned short* s = x + n_ * 3 * hw + p;
+        u16x4 v{s[0], s[hw], s[2 * hw], 0};
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            if (av[c] != 1.f || bv[c] != 0.f) v[c] = to_h<F16>(av[c] * to_f32<F16>(v[c]) + bv[c]);
+        *reinterpret_cast<u16x4*>(frame + ((n_ * H + y) * Wf + xx) * 4) = v;
+    }
+}
+
 // torchvision AlexNet's five convolutions (torchvision/models/alexnet.py): the only shapes eegclip_convrelu16 takes
 struct mn_layer { int KS, stride, pad, Cin, Cout; };
 static const mn_layer MN_LAYERS[5] = {{11, 4, 2, 3, 64}, {5, 1, 2, 64, 192}, {3, 1, 1, 192, 384}, {3, 1, 1, 384, 256}, {3, 1, 1, 256, 256}};
@@ -384,10 +484,9 @@ static int mn_geometry(mn_args& a, const mn_layer& L, int N, int Hi, int Wi, int
     return 0;
 }
 
-// .. and the launch
+// .. and the launch, N tiles of 64 nj channels
 template <class ARGS>
-static int mn_launch(const ARGS& a, int dtype, void* stream) {
-    const int nj = a.Cout % 128 == 0 ? 2 : 1;
+static int mn_launch_nj(const ARGS& a, int nj, int dtype, void* stream) {
     const size_t lds = 2 * (size_t)(MN_A_B + 64 * nj * MN_ROWB);
     const dim3 grid((unsigned)(8 * a.chunk)), block(512);
     const bool f16 = dtype == EEGCLIP_DT_F16;
@@ -399,6 +498,11 @@ static int mn_launch(const ARGS& a, int dtype, void* stream) {
         else     EEG_LAUNCH((convrelu16_kernel<false, 1, ARGS>), grid, block, lds, stream, a);
     }
     return (int)hipGetLastError();
+}
+
+template <class ARGS>
+static int mn_launch(const ARGS& a, int dtype, void* stream) {
+    return mn_launch_nj(a, a.Cout % 128 == 0 ? 2 : 1, dtype, stream);
 }
 
 static unsigned mn_grid(long long threads) {
@@ -554,5 +658,96 @@ extern "C" int eegclip_pack_nchw16_pad1(const void* x, void* frame, int N, int H
     if ((reinterpret_cast<uintptr_t>(x) & 1u) || (reinterpret_cast<uintptr_t>(frame) & 15u)) return EEGCLIP_EALIGN;
     EEG_LAUNCH((pack_nchw16_kernel<1>), dim3(mn_grid((long long)N * H * W)), dim3(256), 0, stream, static_cast<const unsigned short*>(x),
                static_cast<unsigned short*>(frame), N, H, W, mn_first_width(W, MN_EFF_STEM));
+    return (int)hipGetLastError();
+}
+
+// ---- the Inception row (torchvision/models/inception.py): convolution + BatchNorm + ReLU into a channel slice of a concatenated frame
+static const mn_layer MN_INC_STEM = {3, 2, 0, 3, 64};        // Conv2d_1a_3x3 (32 filters; rows 32 .. 63 of the packed weight are zero and never stored)
+
+extern "C" int eegclip_convbncat16_in_width(int Wi) { return Wi < 3 ? EEGCLIP_EINVAL : mn_first_width(Wi, MN_INC_STEM); }
+
+extern "C" int eegclip_convbncat16(const eegclip_convbncat16_desc* d, void* stream) {
+    if (!d || !d->in || !d->W || !d->scale || !d->shift || !d->out || d->N < 1 || d->Hi < 1 || d->Wi < 1 || d->out_pad < 0 || d->out_pad > 3 || d->in_pad < 0 ||
+        d->in_pad > 3 || (d->relu != 0 && d->relu != 1) || !half_dtype_ok(d->dtype))
+        return EEGCLIP_EINVAL;
+    const int KH = d->KH, KW = d->KW, ph = d->pad_h, pw = d->pad_w;
+    // the kernel shapes of the net: a square 3 x 3 unpadded (stride 1 or 2) or padded by 1, every other shape with its "same" padding on each axis, stride 1
+    bool shape = false;
+    if (KH == 3 && KW == 3) shape = (ph == 0 && pw == 0 && (d->stride == 1 || d->stride == 2)) || (ph == 1 && pw == 1 && d->stride == 1);
+    else if ((KH == 1 && (KW == 1 || KW == 3 || KW == 7)) || (KW == 1 && (KH == 3 || KH == 7)) || (KH == 5 && KW == 5))
+        shape = ph == KH / 2 && pw == KW / 2 && d->stride == 1;
+    if (!shape || d->Cout < 8 || d->Cout % 8 || d->out_c0 < 0 || d->out_c0 % 8 || d->out_stride % 8 || (long long)d->out_c0 + d->Cout > d->out_stride)
+        return EEGCLIP_EINVAL;
+    const bool first = d->Cin == 3;
+    if (first ? !(KH == 3 && d->stride == 2 && d->in_pad == 0 && d->Cout <= 64) : (d->Cin < 64 || d->Cin % 64 || d->in_pad < (ph > pw ? ph : pw)))
+        return EEGCLIP_EINVAL;
+    if (d->Hi + 2 * ph < KH || d->Wi + 2 * pw < KW) return EEGCLIP_EINVAL;
+    mn_cat_args a;
+    a.W = static_cast<const unsigned short*>(d->W);
+    a.bias = nullptr;
+    a.out = static_cast<unsigned short*>(d->out);
+    a.scale = static_cast<const float*>(d->scale);
+    a.shift = static_cast<const float*>(d->shift);
+    a.relu = d->relu; a.ostride = d->out_stride; a.oc0 = d->out_c0;
+    const int Ho = (d->Hi + 2 * ph - KH) / d->stride + 1, Wo = (d->Wi + 2 * pw - KW) / d->stride + 1;
+    a.Ho = Ho; a.Wo = Wo;
+    a.Hp = d->Hi + 2 * d->in_pad;
+    a.Wp = first ? mn_first_width(d->Wi, MN_INC_STEM) : d->Wi + 2 * d->in_pad;
+    a.pix = first ? 4 : d->Cin;
+    a.Hop = Ho + 2 * d->out_pad; a.Wop = Wo + 2 * d->out_pad; a.opad = d->out_pad; a.Cout = d->Cout;
+    a.KH = KH; a.KW = first ? 1 : KW; a.kc = first ? MN_K : d->Cin; a.stride = d->stride;
+    const long long M = (long long)d->N * Ho * Wo;
+    if (M > 0x7fffffffLL || (long long)d->N * a.Hp * a.Wp * a.pix > 0x7fffffffLL) return EEGCLIP_EINVAL;
+    a.M = (int)M;
+    const int cpad = (d->Cout + 63) / 64 * 64, nj = cpad % 128 == 0 ? 2 : 1;
+    a.tiles_n = cpad / (64 * nj);
+    a.ntiles = a.tiles_n * ((a.M + MN_T - 1) / MN_T);
+    a.chunk = (a.ntiles + 7) / 8;
+    // the tile loop walks the frame from its pixel (in_pad - pad_h, in_pad - pad_w): a 1 x 7 and a 7 x 1 layer read the same border-3 frame
+    a.in = static_cast<const unsigned short*>(d->in) + ((long long)(d->in_pad - ph) * a.Wp + (d->in_pad - pw)) * a.pix;
+    if ((reinterpret_cast<uintptr_t>(d->in) | reinterpret_cast<uintptr_t>(d->W)) & 15u) return EEGCLIP_EALIGN;
+    if (reinterpret_cast<uintptr_t>(d->out) & 7u) return EEGCLIP_EALIGN;
+    if ((reinterpret_cast<uintptr_t>(d->scale) | reinterpret_cast<uintptr_t>(d->shift)) & 3u) return EEGCLIP_EALIGN;
+    return mn_launch_nj(a, nj, d->dtype, stream);
+}
+
+extern "C" int eegclip_avgpool3x3_16(const void* in, void* out, int N, int H, int W, int C, int in_pad, int dtype, void* stream) {
+    if (!in || !out || N < 1 || H < 1 || W < 1 || C < 8 || C % 8 || in_pad < 1 || in_pad > 3 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) return EEGCLIP_EALIGN;
+    const dim3 grid(mn_grid((long long)N * H * W * (C / 8)));
+    const unsigned short* i16 = static_cast<const unsigned short*>(in);
+    unsigned short* o16 = static_cast<unsigned short*>(out);
+    if (dtype == EEGCLIP_DT_F16) EEG_LAUNCH((avgpool3x3_16_kernel<true>), grid, dim3(256), 0, stream, i16, o16, N, H, W, C, in_pad);
+    else                         EEG_LAUNCH((avgpool3x3_16_kernel<false>), grid, dim3(256), 0, stream, i16, o16, N, H, W, C, in_pad);
+    return (int)hipGetLastError();
+}
+
+extern "C" int eegclip_maxpool16_cat(const void* in, void* out, int N, int H, int W, int C, int in_stride, int in_pad, int out_stride, int out_c0, int out_pad,
+                                     int dtype, void* stream) {
+    if (!in || !out || N < 1 || H < 3 || W < 3 || C < 8 || C % 8 || in_stride < C || in_stride % 8 || out_c0 < 0 || out_c0 % 8 || out_stride % 8 ||
+        (long long)out_c0 + C > out_stride || in_pad < 0 || in_pad > 3 || out_pad < 0 || out_pad > 3 || !half_dtype_ok(dtype))
+        return EEGCLIP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) return EEGCLIP_EALIGN;
+    const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
+    const dim3 grid(mn_grid((long long)N * Ho * Wo * (C / 8)));
+    const unsigned short* i16 = static_cast<const unsigned short*>(in);
+    unsigned short* o16 = static_cast<unsigned short*>(out);
+    if (dtype == EEGCLIP_DT_F16)
+        EEG_LAUNCH((maxpool16_cat_kernel<true>), grid, dim3(256), 0, stream, i16, o16, N, H, W, C, in_stride, in_pad, out_stride, out_c0, out_pad, Ho, Wo);
+    else
+        EEG_LAUNCH((maxpool16_cat_kernel<false>), grid, dim3(256), 0, stream, i16, o16, N, H, W, C, in_stride, in_pad, out_stride, out_c0, out_pad, Ho, Wo);
+    return (int)hipGetLastError();
+}
+
+extern "C" int eegclip_pack_nchw16_affine(const void* x, void* frame, const float* a, const float* b, int N, int H, int W, int dtype, void* stream) {
+    if (!x || !frame || !a || !b || N < 1 || H < 3 || W < 3 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(x) & 1u) || (reinterpret_cast<uintptr_t>(frame) & 15u)) return EEGCLIP_EALIGN;
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3u) return EEGCLIP_EALIGN;
+    const dim3 grid(mn_grid((long long)N * H * W));
+    const unsigned short* x16 = static_cast<const unsigned short*>(x);
+    unsigned short* f16 = static_cast<unsigned short*>(frame);
+    const int wf = mn_first_width(W, MN_INC_STEM);
+    if (dtype == EEGCLIP_DT_F16) EEG_LAUNCH((pack_nchw16_affine_kernel<true>), grid, dim3(256), 0, stream, x16, f16, a, b, N, H, W, wf);
+    else                         EEG_LAUNCH((pack_nchw16_affine_kernel<false>), grid, dim3(256), 0, stream, x16, f16, a, b, N, H, W, wf);
     return (int)hipGetLastError();
 }

@@ -1,5 +1,6 @@
 """The feature nets of the reference's metrics table that this package carries: torchvision's AlexNet up to `features.11`, a ResNet-50 trunk up to
-`avgpool` (the SwAV row) and EfficientNet-B1 up to `avgpool` (the EffNet-B row; EfficientNetFeatures below), on HIP kernels (csrc/metric_nets.hip, csrc/mbconv.hip).  The metrics notebooks under Generation/ (copies of MindEye's Reconstruction_Metrics) take alexnet(weights=IMAGENET1K_V1)
+`avgpool` (the SwAV row), EfficientNet-B1 up to `avgpool` (the EffNet-B row; EfficientNetFeatures below) and InceptionV3 up to `avgpool` (the Inception row;
+InceptionFeatures below), on HIP kernels (csrc/metric_nets.hip, csrc/mbconv.hip).  The metrics notebooks under Generation/ (copies of MindEye's Reconstruction_Metrics) take alexnet(weights=IMAGENET1K_V1)
 through create_feature_extractor at `features.4` (the AlexNet(2) row) and `features.11` (the AlexNet(5) row) and score both by two-way identification.
 
 AlexNetFeatures is the architecture in torchvision's key layout with seeded random weights, as every model of this package: load the real checkpoint
@@ -504,3 +505,256 @@ class EfficientNetFeatures(nn.Module):
 def efficientnet_b1(**kw):
     """the EfficientNet-B1 trunk of the metrics table's EffNet-B row (torchvision's efficientnet_b1 without its classifier), seeded weights"""
     return EfficientNetFeatures(layers=EFF_B1_LAYERS, **kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- InceptionV3 trunk (the Inception row)
+# torchvision/models/inception.py.  A branch is a chain of BasicConv2d layers (name, Cout, (KH, KW), stride, (pad_h, pad_w)); the last layer(s) of a chain write
+# their slice of the block's output frame.  "pool" stands for the block's pooling branch.
+MIN_SIDE_INCEPTION = 75                         # 75 -> 37 -> 35 -> 35 -> 17 -> 17 -> 15 -> 7 (Mixed_5*) -> 3 (Mixed_6*) -> 1 (Mixed_7*); at 74 Mixed_7a meets 2 x 2
+INC_A_POOL, INC_C_MID = (32, 64, 64), (128, 160, 160, 192)
+INC_NAMES = {"A": ("Mixed_5b", "Mixed_5c", "Mixed_5d"), "B": ("Mixed_6a",), "C": ("Mixed_6b", "Mixed_6c", "Mixed_6d", "Mixed_6e"), "D": ("Mixed_7a",),
+             "E": ("Mixed_7b", "Mixed_7c")}
+INC_STEM = (("Conv2d_1a_3x3", 3, 32, 3, 2, 0), ("Conv2d_2a_3x3", 32, 32, 3, 1, 0), ("Conv2d_2b_3x3", 32, 64, 3, 1, 1), ("Conv2d_3b_1x1", 64, 80, 1, 1, 0),
+            ("Conv2d_4a_3x3", 80, 192, 3, 1, 0))
+INC_MEAN, INC_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def inception_block_layers(kind, cin, arg=None):
+    """[(name, Cin, Cout, (KH, KW), stride, (pad_h, pad_w))] of a block in torchvision's registration order; arg: pool_features (A) or channels_7x7 (C)"""
+    sq = lambda n, i, o, k, s=1, p=0: (n, i, o, (k, k), s, (p, p))   # noqa: E731
+    if kind == "A":
+        return [sq("branch1x1", cin, 64, 1), sq("branch5x5_1", cin, 48, 1), sq("branch5x5_2", 48, 64, 5, 1, 2), sq("branch3x3dbl_1", cin, 64, 1),
+                sq("branch3x3dbl_2", 64, 96, 3, 1, 1), sq("branch3x3dbl_3", 96, 96, 3, 1, 1), sq("branch_pool", cin, arg, 1)]
+    if kind == "B":
+        return [sq("branch3x3", cin, 384, 3, 2), sq("branch3x3dbl_1", cin, 64, 1), sq("branch3x3dbl_2", 64, 96, 3, 1, 1), sq("branch3x3dbl_3", 96, 96, 3, 2)]
+    row, col = lambda n, i, o, k: (n, i, o, (1, k), 1, (0, k // 2)), lambda n, i, o, k: (n, i, o, (k, 1), 1, (k // 2, 0))   # noqa: E731
+    if kind == "C":
+        c = arg
+        return [sq("branch1x1", cin, 192, 1), sq("branch7x7_1", cin, c, 1), row("branch7x7_2", c, c, 7), col("branch7x7_3", c, 192, 7),
+                sq("branch7x7dbl_1", cin, c, 1), col("branch7x7dbl_2", c, c, 7), row("branch7x7dbl_3", c, c, 7), col("branch7x7dbl_4", c, c, 7),
+                row("branch7x7dbl_5", c, 192, 7), sq("branch_pool", cin, 192, 1)]
+    if kind == "D":
+        return [sq("branch3x3_1", cin, 192, 1), sq("branch3x3_2", 192, 320, 3, 2), sq("branch7x7x3_1", cin, 192, 1), row("branch7x7x3_2", 192, 192, 7),
+                col("branch7x7x3_3", 192, 192, 7), sq("branch7x7x3_4", 192, 192, 3, 2)]
+    return [sq("branch1x1", cin, 320, 1), sq("branch3x3_1", cin, 384, 1), row("branch3x3_2a", 384, 384, 3), col("branch3x3_2b", 384, 384, 3),
+            sq("branch3x3dbl_1", cin, 448, 1), sq("branch3x3dbl_2", 448, 384, 3, 1, 1), row("branch3x3dbl_3a", 384, 384, 3), col("branch3x3dbl_3b", 384, 384, 3),
+            sq("branch_pool", cin, 192, 1)]
+
+
+# how a block runs: per launch (layer name | "pool", source, destination); sources / destinations are "in" (the block's input frame), "out" (a slice of its output
+# frame, in the order of concatenation) or a temporary's name
+INC_FLOW = {
+    "A": (("branch1x1", "in", "out"), ("branch5x5_1", "in", "a"), ("branch5x5_2", "a", "out"), ("branch3x3dbl_1", "in", "a"), ("branch3x3dbl_2", "a", "b"),
+          ("branch3x3dbl_3", "b", "out"), ("pool", "in", "p"), ("branch_pool", "p", "out")),
+    "B": (("branch3x3", "in", "out"), ("branch3x3dbl_1", "in", "a"), ("branch3x3dbl_2", "a", "b"), ("branch3x3dbl_3", "b", "out"), ("pool", "in", "out")),
+    "C": (("branch1x1", "in", "out"), ("branch7x7_1", "in", "a"), ("branch7x7_2", "a", "b"), ("branch7x7_3", "b", "out"), ("branch7x7dbl_1", "in", "a"),
+          ("branch7x7dbl_2", "a", "b"), ("branch7x7dbl_3", "b", "a"), ("branch7x7dbl_4", "a", "b"), ("branch7x7dbl_5", "b", "out"), ("pool", "in", "p"),
+          ("branch_pool", "p", "out")),
+    "D": (("branch3x3_1", "in", "a"), ("branch3x3_2", "a", "out"), ("branch7x7x3_1", "in", "a"), ("branch7x7x3_2", "a", "b"), ("branch7x7x3_3", "b", "a"),
+          ("branch7x7x3_4", "a", "out"), ("pool", "in", "out")),
+    "E": (("branch1x1", "in", "out"), ("branch3x3_1", "in", "a"), ("branch3x3_2a", "a", "out"), ("branch3x3_2b", "a", "out"), ("branch3x3dbl_1", "in", "a"),
+          ("branch3x3dbl_2", "a", "b"), ("branch3x3dbl_3a", "b", "out"), ("branch3x3dbl_3b", "b", "out"), ("pool", "in", "p"), ("branch_pool", "p", "out")),
+}
+
+
+class _BasicConv2d(nn.Module):
+    """torchvision's BasicConv2d as a holder of parameters (never called): `conv` without bias, `bn` with eps = 0.001; a ReLU follows"""
+
+    def __init__(self, cin, cout, kernel, stride, padding):
+        super().__init__()
+        self.conv, self.bn = nn.Conv2d(cin, cout, kernel, stride, padding, bias=False), nn.BatchNorm2d(cout, eps=0.001)
+
+
+class _InceptionBlock(nn.Module):
+    def __init__(self, kind, cin, arg=None):
+        super().__init__()
+        self.kind, self.cin = kind, cin
+        layers = inception_block_layers(kind, cin, arg)
+        for name, i, o, k, s, p in layers:
+            setattr(self, name, _BasicConv2d(i, o, k, s, p))
+        sliced = [getattr(self, n).conv.out_channels for n, _, dst in INC_FLOW[kind] if dst == "out" and n != "pool"]
+        self.cout = sum(sliced) + (cin if kind in "BD" else 0)     # (B and D concatenate the max-pooled input)
+
+
+class InceptionFeatures(nn.Module):
+    """torchvision's Inception3 up to `avgpool` (no AuxLogits, no fc), in torchvision's key layout: the notebooks take inception_v3(weights=DEFAULT) -- so
+    transform_input=True -- at `avgpool`, flatten to (N, 2048) and score two-way identification.  inception_v3() is the (3, 4, 2) net; load the real checkpoint
+    with load_state_dict(torchvision.models.inception_v3(weights="DEFAULT").state_dict()).  blocks = (InceptionA, InceptionC, InceptionE blocks kept, from the
+    front of each group); a block's input width is its predecessor's output width.
+
+    A block's output is ONE frame of pad64(total) channels per pixel: every branch's last convolution (and the max-pool branch of Mixed_6a / Mixed_7a) writes its
+    own channel slice through eegclip_convbncat16 / eegclip_maxpool16_cat, so nothing is concatenated or copied; pad channels (288 -> 320, 736 -> 768) stay the
+    zeros the frame was allocated with and meet zero weight columns.  One forward of a chunk at full depth is 109 launches: the pack (with transform_input's
+    affine), 94 convolutions, the two stem max-pools, 9 average pools 3 x 3, 2 max-pool branches and the global average pool -- no torch arithmetic between.
+    There is no eager path."""
+
+    def __init__(self, blocks=(3, 4, 2), transform_input=True, dtype=torch.float16, device="cuda", seed=0):
+        super().__init__()
+        if len(blocks) != 3 or any(int(n) < 1 for n in blocks) or blocks[0] > 3 or blocks[1] > 4 or blocks[2] > 2:
+            raise EegclipError(f"InceptionFeatures takes (1..3, 1..4, 1..2) InceptionA / C / E blocks; got {blocks}")
+        self.blocks, self.transform_input = tuple(int(n) for n in blocks), bool(transform_input)
+        with seeded_parameters(self, dtype, seed=seed):
+            for name, cin, cout, k, s, p in INC_STEM:
+                setattr(self, name, _BasicConv2d(cin, cout, k, s, p))
+            c, self.order = 192, []
+            for kind, n, args in (("A", self.blocks[0], INC_A_POOL), ("B", 1, (None,)), ("C", self.blocks[1], INC_C_MID), ("D", 1, (None,)),
+                                  ("E", self.blocks[2], (None, None))):
+                for i in range(n):
+                    blk = _InceptionBlock(kind, c, args[i])
+                    setattr(self, INC_NAMES[kind][i], blk)
+                    self.order.append(INC_NAMES[kind][i])
+                    c = blk.cout
+            self.out_features = c
+            # He's draw for the convolutions and BatchNorm away from the identity, as the other nets.  The gain is drawn from (0.7, 1.4): with the other nets'
+            # (0.5, 1.25) the 3 x 3 average pools and 1 / sqrt(var) shrink the signal at every block until `avgpool` is the BatchNorm shifts' alone (its spread
+            # over images falls below fp16's rounding); with (0.75, 1.5) it grows to hundreds at 342 x 342.  Here the fp64 chain peaks below 100.
+            for m in self.modules():
+                if isinstance(m, nn.Conv2d):
+                    nn.init.normal_(m.weight, 0.0, math.sqrt(2.0 / (m.in_channels * m.kernel_size[0] * m.kernel_size[1])))
+                elif isinstance(m, nn.BatchNorm2d):
+                    nn.init.uniform_(m.weight, 0.7, 1.4)
+                    nn.init.uniform_(m.bias, -0.25, 0.25)
+                    nn.init.uniform_(m.running_mean, -0.25, 0.25)
+                    nn.init.uniform_(m.running_var, 0.5, 1.5)
+        for m in self.modules():                                  # BatchNorm tensors are fp32, as in ResNetFeatures
+            if isinstance(m, nn.BatchNorm2d):
+                m.float()
+        self.to(device)
+        self._packed, self._frames = PackedWeights(), {}
+
+    @property
+    def dtype(self):
+        return self.Conv2d_1a_3x3.conv.weight.dtype
+
+    @property
+    def device(self):
+        return self.Conv2d_1a_3x3.conv.weight.device
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """torchvision's Inception3 keys without `AuxLogits` and `fc`; a full torchvision state dict loads too: its AuxLogits.* and fc.* keys are dropped.  Any
+        other unknown or missing key is an error (strict)."""
+        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith(("AuxLogits.", "fc."))}, strict=strict, **kw)
+
+    def _layer(self, tag, layer, cin_pad):
+        """(packed weight, scale, shift) of a BasicConv2d: [pad64(Cout)][KH][KW][cin_pad] with zero rows / columns in the padding -- for the first layer
+        [64][ky][64] with element 4 kx + ci -- and eval-mode BatchNorm as fp32 [pad64(Cout)] vectors, zero in the padding"""
+        conv, bn = layer.conv, layer.bn
+
+        def make():
+            w = conv.weight.detach()
+            cout, cin, kh, kw = w.shape
+            if cin == 3:
+                p = torch.zeros(pad64(cout), kh, 16, 4, dtype=w.dtype, device=w.device)
+                p[:cout, :, :kw, :3] = w.permute(0, 2, 3, 1)
+            else:
+                p = torch.zeros(pad64(cout), kh, kw, cin_pad, dtype=w.dtype, device=w.device)
+                p[:cout, :, :, :cin] = w.permute(0, 2, 3, 1)
+            return (p.reshape(p.shape[0], -1).contiguous(), *EfficientNetFeatures._scale_shift(bn, pad64(cout)))
+        return self._packed.get((tag, cin_pad), (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), make)
+
+    def _affine(self):
+        """transform_input as fp32 (a, b) [3] on the device: torchvision's x_c (std_c / 0.5) + (mean_c - 0.5) / 0.5; the identity without it"""
+        key = ("affine", self.transform_input, self.device)
+        if key not in self._frames:
+            a = [s / 0.5 for s in INC_STD] if self.transform_input else [1.0] * 3
+            b = [(m - 0.5) / 0.5 for m in INC_MEAN] if self.transform_input else [0.0] * 3
+            self._frames[key] = torch.tensor([a, b], dtype=torch.float32, device=self.device)
+        return self._frames[key]
+
+    def _frame(self, role, nb, h, w, c, pad):
+        """a zero-initialised frame [nb][h + 2 pad][w + 2 pad][pad64(c)], kept between calls under (role, its shape, c): no launch writes a border or a pad
+        channel, and a role always writes the same channels, so the interior is simply overwritten"""
+        key = (role, h, w, c, pad)
+        f = self._frames.get(key)
+        if f is None or f.shape[0] < nb or f.dtype != self.dtype or f.device != self.device:
+            f = self._frames[key] = torch.zeros((nb, h + 2 * pad, w + 2 * pad, pad64(c)), dtype=self.dtype, device=self.device)
+        return f[:nb], pad
+
+    def _conv(self, tag, layer, src, dst, c0, nb, h, w):
+        """one BasicConv2d launch from frame `src` = (tensor, border) at h x w into channels c0 .. of frame `dst`"""
+        (s, in_pad), (d, out_pad), conv = src, dst, layer.conv
+        first = conv.in_channels == 3
+        wt, scale, shift = self._layer(tag, layer, 4 if first else s.shape[3])
+        desc = _abi.ConvBnCat16Desc(in_=s.data_ptr(), W=wt.data_ptr(), scale=scale.data_ptr(), shift=shift.data_ptr(), out=d.data_ptr(), N=nb, Hi=h, Wi=w,
+                                    Cin=3 if first else s.shape[3], Cout=conv.out_channels, KH=conv.kernel_size[0], KW=conv.kernel_size[1],
+                                    stride=conv.stride[0], pad_h=conv.padding[0], pad_w=conv.padding[1], in_pad=in_pad, out_pad=out_pad, out_stride=d.shape[3],
+                                    out_c0=c0, relu=1, dtype=dtype_code(self.dtype))
+        check(lib().eegclip_convbncat16(desc, raw_stream()), f"convbncat16 ({tag}, {nb} x {h} x {w})")
+
+    def _block(self, name, blk, cur, nb, h, w, out_pad, parity):
+        """one Inception block from frame `cur` -> (its output frame, ho, wo)"""
+        kind, L, dt = blk.kind, lib(), dtype_code(self.dtype)
+        ho, wo = (pool_out(h), pool_out(w)) if kind in "BD" else (h, w)
+        out = self._frame(f"mixed.{parity}", nb, ho, wo, blk.cout, out_pad)
+        flow = INC_FLOW[kind]
+        c0, tmp = 0, {"in": cur}
+        for j, (lname, src, dst) in enumerate(flow):
+            if lname == "pool" and kind in "BD":                  # MaxPool2d(3, 2) of the input, a branch of the concatenation
+                check(L.eegclip_maxpool16_cat(cur[0].data_ptr(), out[0].data_ptr(), nb, h, w, blk.cin, cur[0].shape[3], cur[1], out[0].shape[3], c0, out_pad, dt,
+                                              raw_stream()), f"maxpool16_cat ({name}, {nb} x {h} x {w} x {blk.cin})")
+                c0 += blk.cin
+                continue
+            if lname == "pool":                                   # avg_pool2d(3, 1, 1) of the input, pad channels included (they are zero)
+                tmp["p"] = self._frame("avg", nb, h, w, cur[0].shape[3], 0)
+                check(L.eegclip_avgpool3x3_16(cur[0].data_ptr(), tmp["p"][0].data_ptr(), nb, h, w, cur[0].shape[3], cur[1], dt, raw_stream()),
+                      f"avgpool3x3_16 ({name}, {nb} x {h} x {w} x {cur[0].shape[3]})")
+                continue
+            layer = getattr(blk, lname)
+            if dst == "out":
+                self._conv(f"{name}.{lname}", layer, tmp[src], out, c0, nb, h, w)
+                c0 += layer.conv.out_channels
+                continue
+            # a temporary carries the border its reader pads by (readers of one temporary agree: the two halves of InceptionE's split read 1 x 3 and 3 x 1)
+            rewritten = next((i for i in range(j + 1, len(flow)) if flow[i][2] == dst), len(flow) - 1)
+            pad = max(max(getattr(blk, n).conv.padding) for n, s2, _ in flow[j + 1:rewritten + 1] if s2 == dst)
+            tmp[dst] = self._frame(f"tmp.{dst}", nb, h, w, layer.conv.out_channels, pad)
+            self._conv(f"{name}.{lname}", layer, tmp[src], tmp[dst], 0, nb, h, w)
+        assert c0 == blk.cout
+        return out, ho, wo
+
+    def forward(self, x, chunk=64):
+        """x: (B, 3, H, W), normalised (preprocess.inception_preprocess), of this net's dtype and on its device -> (B, 2048) fp32: the `avgpool` node, flattened.
+        H, W >= MIN_SIDE_INCEPTION = 75.  The batch runs `chunk` images at a time through frames that are reused, so only the result grows with B."""
+        require_cuda(x, "x")
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.dtype != self.dtype or x.device != self.device:
+            raise EegclipError(f"InceptionFeatures takes (B, 3, H, W) {self.dtype} on {self.device}; got {tuple(x.shape)} {x.dtype} on {x.device}")
+        B, _, H, W = x.shape
+        if min(H, W) < MIN_SIDE_INCEPTION or chunk < 1:
+            raise EegclipError(f"InceptionFeatures needs images of at least {MIN_SIDE_INCEPTION} x {MIN_SIDE_INCEPTION} and chunk >= 1; got {H} x {W}, chunk {chunk}")
+        x = x.contiguous()
+        L, dt = lib(), dtype_code(self.dtype)
+        out = torch.empty(B, self.out_features, dtype=torch.float32, device=self.device)
+        wf, ab = L.eegclip_convbncat16_in_width(W), self._affine()
+        blocks = [(n, getattr(self, n)) for n in self.order]
+        for b0 in range(0, B, chunk):
+            nb = min(chunk, B - b0)
+            f0 = self._frames.get(("in", H, wf))
+            if f0 is None or f0.shape[0] < nb or f0.dtype != self.dtype or f0.device != self.device:
+                f0 = self._frames[("in", H, wf)] = torch.zeros((nb, H, wf, 4), dtype=self.dtype, device=self.device)
+            f0 = f0[:nb]
+            check(L.eegclip_pack_nchw16_affine(x[b0:b0 + nb].data_ptr(), f0.data_ptr(), ab[0].data_ptr(), ab[1].data_ptr(), nb, H, W, dt, raw_stream()),
+                  f"pack_nchw16_affine ({nb} x {H} x {W})")
+            cur, h, w = (f0, 0), H, W
+            # the stem: a frame's border is what its reader pads by (Conv2d_2b_3x3 pads by 1; the first Inception block's average pool reads a border of 1)
+            for i, (name, _, cout, k, s, p) in enumerate(INC_STEM):
+                ho, wo = conv_out(h, k, s, p), conv_out(w, k, s, p)
+                nxt = self._frame(f"stem.{i}", nb, ho, wo, cout, INC_STEM[i + 1][5] if i + 1 < len(INC_STEM) else 0)
+                self._conv(name, getattr(self, name), cur, nxt, 0, nb, h, w)
+                cur, h, w = nxt, ho, wo
+                if name in ("Conv2d_2b_3x3", "Conv2d_4a_3x3"):    # maxpool1, maxpool2
+                    ho, wo = pool_out(h), pool_out(w)
+                    last = name == "Conv2d_4a_3x3"
+                    nxt = self._frame(f"pool.{i}", nb, ho, wo, cout, 1 if last else 0)
+                    check(L.eegclip_maxpool16(cur[0].data_ptr(), nxt[0].data_ptr(), nb, h, w, cur[0].shape[3], 0, nxt[1], dt, raw_stream()),
+                          f"maxpool16 ({nb} x {h} x {w} x {cur[0].shape[3]})")
+                    cur, h, w = nxt, ho, wo
+            for idx, (name, blk) in enumerate(blocks):
+                nxt_kind = blocks[idx + 1][1].kind if idx + 1 < len(blocks) else None
+                cur, h, w = self._block(name, blk, cur, nb, h, w, 1 if nxt_kind in ("A", "C", "E") else 0, idx & 1)
+            check(L.eegclip_avgpool16(cur[0].data_ptr(), out[b0:b0 + nb].data_ptr(), nb, h, w, self.out_features, dt, raw_stream()), f"avgpool16 ({nb} x {h} x {w})")
+        return out
+
+
+def inception_v3(**kw):
+    """the InceptionV3 trunk of the metrics table's Inception row (torchvision's inception_v3 without AuxLogits and fc, transform_input=True), seeded weights"""
+    return InceptionFeatures(blocks=(3, 4, 2), **kw)

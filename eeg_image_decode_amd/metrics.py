@@ -9,12 +9,13 @@ Reconstruction_Metrics): PixCorr, SSIM and two-way identification, on images and
 * correlation_distance(real, recon)   scipy.spatial.distance.correlation of every pair of rows, the score of the notebooks' "distance" rows (EffNet-B, SwAV);
 * swav_distance(images, recons, net)  the SwAV row: the mean of that on the `avgpool` node of a metric_nets.ResNetFeatures (swav_resnet50);
 * effnet_distance(images, recons, net) the EffNet-B row: the same mean on the `avgpool` node of a metric_nets.EfficientNetFeatures (efficientnet_b1);
-* reconstruction_metrics(...)         the table: {"PixCorr", "SSIM"}, the two AlexNet rows, the SwAV row and the EffNet-B row when their nets are given, and
-                                      one two-way entry per feature net handed in.
+* inception_two_way(images, recons, net) the Inception row: two-way identification on the `avgpool` node of a metric_nets.InceptionFeatures (inception_v3);
+* reconstruction_metrics(...)         the table: {"PixCorr", "SSIM"}, the two AlexNet rows, the SwAV row, the EffNet-B row and the Inception row when their nets
+                                      are given, and one two-way entry per feature net handed in (the CLIP row is such an entry around a tower of this package).
 
-AlexNet's, the SwAV ResNet-50's and EfficientNet-B1's architectures are carried (metric_nets.py, csrc/metric_nets.hip, csrc/mbconv.hip) with seeded weights:
-load torchvision's IMAGENET1K_V1 state dicts / the SwAV checkpoint into them for the notebooks' rows.  The InceptionV3 row stays out: hand any callable
-`images -> features` in as a feature net.
+AlexNet's, the SwAV ResNet-50's, EfficientNet-B1's and InceptionV3's architectures are carried (metric_nets.py, csrc/metric_nets.hip, csrc/mbconv.hip) with
+seeded weights: load torchvision's state dicts / the SwAV checkpoint into them for the notebooks' rows.  With a CLIP tower as a feature net, all eight rows of
+the notebooks' table come from this package.
 
 One difference from the notebooks: they resize with torchvision's Resize(425, BILINEAR) on float tensors; here PIL images, uint8 arrays and float tensors of
 another size go through preprocess.resize_crop_normalize(size, filter="bilinear"), PIL's 8-bit antialiased resize (what Resize does to a PIL image), so the
@@ -177,12 +178,23 @@ def effnet_distance(images, recons, net, size=255, return_distances=False):
     return (mean, d) if return_distances else mean
 
 
-def reconstruction_metrics(images, recons, feature_nets=None, size=425, device=None, alexnet=None, swav=None, effnet=None):
+def inception_two_way(images, recons, net, size=342, return_counts=False):
+    """the notebooks' Inception row: two-way identification on the `avgpool` features (N, 2048) of `net` (a metric_nets.InceptionFeatures; inception_v3 with
+    torchvision's weights loaded is the notebooks' net).  Both sides go through preprocess.inception_preprocess(size), float tensors as values in [0, 1].
+    return_counts=True: (score, count (N,) int32 on the device)."""
+    feats = []
+    for x in (images, recons):
+        kw = {"in_range": (0.0, 1.0)} if isinstance(x, torch.Tensor) and x.is_floating_point() else {}
+        feats.append(net(preprocess.inception_preprocess(x, size=size, dtype=net.dtype, device=net.device, **kw)))
+    return two_way_identification(feats[0], feats[1], return_counts=return_counts)
+
+
+def reconstruction_metrics(images, recons, feature_nets=None, size=425, device=None, alexnet=None, swav=None, effnet=None, inception=None):
     """the notebooks' table for N pairs: {"PixCorr": mean, "SSIM": mean} plus, with alexnet= a metric_nets.AlexNetFeatures, "AlexNet(2)" and "AlexNet(5)"
     (alexnet_two_way at its default size 256) plus, with swav= a metric_nets.ResNetFeatures, "SwAV" (swav_distance at its default size 224) plus, with effnet= a
-    metric_nets.EfficientNetFeatures, "EffNet-B" (effnet_distance at its default size 255) plus, per `name: callable` of feature_nets, name: the two-way
-    identification score of callable(images) against callable(recons) (each an (N, ...) feature tensor on the device; e.g. lambda x:
-    tower(preprocess.clip_image_processor(x)).image_embeds).  The Inception row of the notebooks is such a callable around a net this package does not carry."""
+    metric_nets.EfficientNetFeatures, "EffNet-B" (effnet_distance at its default size 255) plus, with inception= a metric_nets.InceptionFeatures, "Inception"
+    (inception_two_way at its default size 342) plus, per `name: callable` of feature_nets, name: the two-way identification score of callable(images) against
+    callable(recons) (each an (N, ...) feature tensor on the device; e.g. the CLIP row: lambda x: tower(preprocess.clip_image_processor(x)).image_embeds)."""
     pix, ssm = pixcorr_ssim(images, recons, size, device)
     out = {"PixCorr": float(pix.mean()), "SSIM": float(ssm.mean())}
     if alexnet is not None:
@@ -191,6 +203,8 @@ def reconstruction_metrics(images, recons, feature_nets=None, size=425, device=N
         out["SwAV"] = swav_distance(images, recons, swav)
     if effnet is not None:
         out["EffNet-B"] = effnet_distance(images, recons, effnet)
+    if inception is not None:
+        out["Inception"] = inception_two_way(images, recons, inception)
     for name, net in (feature_nets or {}).items():
         if name in out:
             raise EegclipError(f"feature net name {name!r} is taken by another row of the table")

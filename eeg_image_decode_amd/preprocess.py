@@ -238,3 +238,10 @@ def effnet_preprocess(images, size=255, **kw):
     """the metrics notebooks' transform in front of EfficientNet-B1: Resize(255, BILINEAR) -- the shortest side becomes `size`, no crop -- and Normalize with
     ImageNet's mean / std: alexnet_preprocess at the EffNet-B row's size, with the same note on PIL's 8-bit resize"""
     return alexnet_preprocess(images, size=size, **kw)
+
+
+def inception_preprocess(images, size=342, **kw):
+    """the metrics notebooks' transform in front of InceptionV3: Resize(342, BILINEAR) -- the shortest side becomes `size`, no crop -- and Normalize with
+    ImageNet's mean / std: alexnet_preprocess at the Inception row's size, with the same note on PIL's 8-bit resize.  (torchvision's transform_input, which
+    undoes this normalisation in favour of (x - 0.5) / 0.5, is part of the net: metric_nets.InceptionFeatures.)"""
+    return alexnet_preprocess(images, size=size, **kw)

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define EEGCLIP_ABI_VERSION 25
+#define EEGCLIP_ABI_VERSION 26
 #define EEGCLIP_EINVAL (-1)   /* bad shape / null pointer / unsupported combination */
 #define EEGCLIP_EALIGN (-2)   /* pointer or stride violates an alignment requirement */
 
@@ -1252,6 +1252,53 @@ int eegclip_dwconv16(const void* in, const void* W, const float* scale, const fl
 int eegclip_se_gate16(const float* pooled, const void* W1, const void* b1, const void* W2, const void* b2, float* gate, int N, int S, int HW, int C, int sq,
                       int dtype, void* stream);
 int eegclip_gate_mul16(void* y, const float* gate, int N, int HW, int C, int dtype, void* stream);
+
+/* ---- the feature net of the metrics table's Inception row (csrc/metric_nets.hip; the reference's metrics notebooks take torchvision's inception_v3 --
+ * torchvision/models/inception.py: BasicConv2d = convolution without bias + BatchNorm(eps = 0.001) + ReLU, blocks that concatenate three or four branches -- at
+ * `avgpool` and score it by two-way identification).  (ABI 26.)  Frames, dtypes and reproducibility as above: no atomics, no memsets, every run bit-identical.
+ * A block's output is ONE frame whose pixels are `out_stride` = pad64(sum of the branches) channels apart; every branch's last launch writes its own channel slice
+ * of it and nothing else, so there is no concatenation launch.  The zero pad channels past the last branch are written by nobody.
+ *   eegclip_convbncat16  out[n][y][x][out_c0 + co] = act(scale[co] * conv(in, W)[n][y][x][co] + shift[co]) for co < Cout, act = ReLU when relu = 1: a fourth
+ *                        instantiation of eegclip_convrelu16's kernel template (fp32 accumulation, one 16-bit rounding at the store).  Kernel shapes
+ *                        (KH, KW; pad_h, pad_w; stride): (3, 3; 0, 0; 1 or 2), (3, 3; 1, 1; 1), and at stride 1 with pad_h = KH / 2, pad_w = KW / 2: (1, 1), (5, 5),
+ *                        (1, 7), (7, 1), (1, 3), (3, 1).  `in`: the frame [N][Hi + 2 in_pad][Wi + 2 in_pad][Cin], Cin % 64 == 0 (the host pads channels with
+ *                        zeros), max(pad_h, pad_w) <= in_pad <= 3; the tile loop starts at frame pixel (in_pad - pad_h, in_pad - pad_w), so a 1 x 7 and a 7 x 1
+ *                        layer read the same border-3 frame and a 1 x 1 layer skips whatever border it meets.  out: the frame
+ *                        [N][Ho + 2 out_pad][Wo + 2 out_pad][out_stride], Ho = (Hi + 2 pad_h - KH) / stride + 1, 0 <= out_pad <= 3; channels out_c0 ..
+ *                        out_c0 + Cout - 1 of its interior pixels are written and NOTHING else (not the border, not the other channels).  Cout % 8 == 0,
+ *                        out_c0 % 8 == 0, out_stride % 8 == 0, out_c0 + Cout <= out_stride.  W: [pad64(Cout)][KH][KW][Cin] with zero rows past Cout; scale,
+ *                        shift: fp32 [pad64(Cout)].  The first layer (Cin = 3: KH = KW = 3, stride 2, pads 0, in_pad = 0, Cout <= 64) takes the frame
+ *                        eegclip_pack_nchw16_affine writes, [N][Hi][eegclip_convbncat16_in_width(Wi)][4], and W [64][3][64] with element 4 kx + ci of row ky,
+ *                        zero where ci = 3 or kx >= 3; the 13 pixels right of a window must be finite.  Anything else: EEGCLIP_EINVAL.  Element offsets into
+ *                        the input frame are 32-bit (EEGCLIP_EINVAL beyond).  EEGCLIP_EALIGN: in / W not 16-byte, out not 8-byte, scale / shift not 4-byte
+ *                        aligned.
+ *   eegclip_avgpool3x3_16  F.avg_pool2d(x, 3, 1, 1) (count_include_pad=True): `in` is the frame [N][H + 2 in_pad][W + 2 in_pad][C], 1 <= in_pad <= 3, whose zero
+ *                        border is read, not tested for; the nine taps are added in fp32 in (ky, kx) order and divided by 9, one rounding at the store into the
+ *                        UNPADDED frame [N][H][W][C].  C % 8 == 0, H, W >= 1, both frames 16-byte aligned.
+ *   eegclip_maxpool16_cat  eegclip_maxpool16 (3 / 2, floor mode, no padding, the stored pattern the largest tap's own, a NaN tap wins) as a branch of a
+ *                        concatenation: it reads channels 0 .. C - 1 of the frame [N][H + 2 in_pad][W + 2 in_pad][in_stride] and writes channels out_c0 ..
+ *                        out_c0 + C - 1 of the interior of [N][Ho + 2 out_pad][Wo + 2 out_pad][out_stride], nothing else.  C, in_stride, out_stride, out_c0
+ *                        % 8 == 0, C <= in_stride, out_c0 + C <= out_stride, H, W >= 3, pads in 0 .. 3, both frames 16-byte aligned.
+ *   eegclip_pack_nchw16_affine  x (N, 3, H, W) planes, 16-bit -> the first layer's frame WITHOUT a border, pixel (y, x) at frame pixel (y, x) as
+ *                        {a[0] c0 + b[0], a[1] c1 + b[1], a[2] c2 + b[2], 0}: torchvision's transform_input (a_c = std_c / 0.5, b_c = (mean_c - 0.5) / 0.5).
+ *                        a, b: fp32 [3] on the device, 4-byte aligned; product and sum in fp32, one rounding; a channel with a = 1, b = 0 is copied as a
+ *                        pattern.  The columns from W up to eegclip_convbncat16_in_width(W) must be zero and are not written.  H, W >= 3. */
+typedef struct {
+    const void* in;
+    const void* W;
+    const void* scale;
+    const void* shift;
+    void* out;
+    int N, Hi, Wi, Cin, Cout;
+    int KH, KW, stride, pad_h, pad_w, in_pad;
+    int out_pad, out_stride, out_c0, relu, dtype;
+} eegclip_convbncat16_desc;
+int eegclip_convbncat16_in_width(int Wi);
+int eegclip_convbncat16(const eegclip_convbncat16_desc* d, void* stream);
+int eegclip_avgpool3x3_16(const void* in, void* out, int N, int H, int W, int C, int in_pad, int dtype, void* stream);
+int eegclip_maxpool16_cat(const void* in, void* out, int N, int H, int W, int C, int in_stride, int in_pad, int out_stride, int out_c0, int out_pad, int dtype,
+                          void* stream);
+int eegclip_pack_nchw16_affine(const void* x, void* frame, const float* a, const float* b, int N, int H, int W, int dtype, void* stream);
 
 /* ---- per-kernel timing by the kernel's own GPU timestamps (bench.py roofline): eegclip_time_next_launch(start, stop) arms a pair of
  * library-owned events for the FIRST kernel the calling thread's next entry point launches (hipExtLaunchKernel start / stop events: what
