@@ -28,6 +28,12 @@
 // concatenated.  The tile loop is the same -- it walks KH and KW separately, so 1 x 7, 7 x 1, 1 x 3 and 3 x 1 layers and per-axis padding are host geometry: the
 // frame walk starts at pixel (in_pad - pad_h, in_pad - pad_w) -- and the N tiles cover pad64(Cout) weight rows, of which the epilogue stores the groups below Cout.
 // With it: the 3 x 3 stride-1 average pool of every block, MaxPool2d(3, 2) as a branch of a concatenation, and the pack with transform_input's affine.
+//
+// The host half is shared by the four rows: one mn_geometry fills the tile loop's arguments for every convolution entry point (each keeps its own whitelist of
+// shapes and its alignment rules), the four 3-channel first layers are one table (MN_FIRST), MaxPool2d(3, 2) is one kernel on a channel slice (a whole frame is
+// the widest slice), the four packs are one kernel with a runtime border and an optional affine, and MN_ELEMENTWISE picks an elementwise kernel's f16 / bf16
+// instantiation.  convrelu16_kernel and its four argument types are NOT part of that folding: each row has a type of its own so that the earlier rows'
+// instantiations stay instruction for instruction what they were.
 #include "silu16.h"
 
 namespace eeg {
@@ -245,37 +251,14 @@ __global__ __launch_bounds__(512) void convrelu16_kernel(const ARGS a) {
     }
 }
 
-// ---- MaxPool2d(3, 2), floor mode, no padding: thread = (output pixel, 8 consecutive channels), 16-byte reads and one 16-byte store.  The running maximum
-// starts from the first tap (the input may be negative everywhere); a NaN tap wins, as in torch.
+// ---- MaxPool2d(3, 2), floor mode, no padding, on a channel slice: it reads the first C channels of a frame whose pixels are `istride` elements apart and
+// writes channels oc0 .. oc0 + C - 1 of the interior of a frame with `ostride` elements per pixel; nothing else is written.  A whole frame is the slice
+// istride = ostride = C, oc0 = 0 (eegclip_maxpool16); Inception's Mixed_6a / Mixed_7a pool the block's input into their branch of the concatenation
+// (eegclip_maxpool16_cat).  thread = (output pixel, 8 consecutive channels), 16-byte reads and one 16-byte store.  The running maximum starts from the first
+// tap (the input may be negative everywhere); a NaN tap wins, as in torch.
 template <bool F16>
 __global__ __launch_bounds__(256) void maxpool16_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out, int N, int H, int W, int C,
-                                                        int ipad, int opad, int Ho, int Wo) {
-    const int c8n = C / 8, Hp = H + 2 * ipad, Wp = W + 2 * ipad, Hop = Ho + 2 * opad, Wop = Wo + 2 * opad;
-    const long long total = (long long)N * Ho * Wo * c8n;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
-        const int c = 8 * (int)(q % c8n);
-        const long long pq = q / c8n;
-        const int x = (int)(pq % Wo), y = (int)((pq / Wo) % Ho), n_ = (int)(pq / ((long long)Wo * Ho));
-        const unsigned short* src = in + (((long long)n_ * Hp + 2 * y + ipad) * Wp + 2 * x + ipad) * C + c;
-        u16x8 best = *reinterpret_cast<const u16x8*>(src);
-#pragma unroll
-        for (int tap = 1; tap < 9; ++tap) {
-            const u16x8 v = *reinterpret_cast<const u16x8*>(src + ((long long)(tap / 3) * Wp + tap % 3) * C);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float f = to_f32<F16>(v[e]), b = to_f32<F16>(best[e]);
-                if (f > b || f != f) best[e] = v[e];
-            }
-        }
-        *reinterpret_cast<u16x8*>(out + (((long long)n_ * Hop + y + opad) * Wop + x + opad) * C + c) = best;
-    }
-}
-
-// ---- the same pool as a BRANCH of a concatenation (Inception's Mixed_6a / Mixed_7a): it reads the first C channels of a frame whose
-// pixels are `istride` elements apart and writes channels oc0 .. oc0 + C - 1 of the interior of a frame with `ostride` elements per pixel.  Nothing else is written.
-template <bool F16>
-__global__ __launch_bounds__(256) void maxpool16_cat_kernel(const unsigned short* __restrict__ in, unsigned short* __restrict__ out, int N, int H, int W, int C,
-                                                            int istride, int ipad, int ostride, int oc0, int opad, int Ho, int Wo) {
+                                                        int istride, int ipad, int ostride, int oc0, int opad, int Ho, int Wo) {
     const int c8n = C / 8, Hp = H + 2 * ipad, Wp = W + 2 * ipad, Hop = Ho + 2 * opad, Wop = Wo + 2 * opad;
     const long long total = (long long)N * Ho * Wo * c8n;
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
@@ -415,78 +398,96 @@ __global__ __launch_bounds__(256) void corr_distance_kernel(const float* __restr
     if (t == 0) out[blockIdx.x] = 1.f - sab / (sqrtf(saa) * sqrtf(sbb));          // a constant row: 0 / 0 = NaN, as scipy gives
 }
 
-// ---- (N, 3, H, W) planes -> a 3-channel layer's frame [N][H + 2 B][Wf][4]: pixel (y, x) at frame (y + B, x + B) as {c0, c1, c2, 0}; a copy of 16-bit patterns.
-// B = 2 in front of AlexNet's 11 x 11 layer, 3 in front of ResNet's 7 x 7 stem, 1 in front of EfficientNet's 3 x 3 stem.
-template <int B>
-__global__ __launch_bounds__(256) void pack_nchw16_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ frame, int N, int H, int W, int Wf) {
+// ---- (N, 3, H, W) planes -> a 3-channel layer's frame [N][H + 2 B][Wf][4]: pixel (y, x) at frame (y + B, x + B) as {c0, c1, c2, 0}.  Without AFFINE it is a
+// copy of 16-bit patterns, whatever the dtype (F16 is not looked at).  With it (torchvision Inception3's transform_input) channel c becomes a_c x_c + b_c, the
+// product and the sum in fp32, one rounding; a channel with a_c = 1 and b_c = 0 is still copied as a pattern (-0 and NaN payloads included), so the identity is
+// the plain pack.
+template <bool AFFINE, bool F16>
+__global__ __launch_bounds__(256) void pack_nchw16_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ frame, const float* __restrict__ a,
+                                                          const float* __restrict__ b, int N, int H, int W, int Wf, int B) {
     const long long hw = (long long)H * W, total = N * hw;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
-        const long long n_ = q / hw, p = q - n_ * hw;
-        const int y = (int)(p / W), xx = (int)(p - (long long)y * W);
-        const unsigned short* s = x + n_ * 3 * hw + p;
-        const u16x4 v{s[0], s[hw], s[2 * hw], 0};
-        *reinterpret_cast<u16x4*>(frame + ((n_ * (H + 2 * B) + y + B) * Wf + xx + B) * 4) = v;
+    float av[3] = {1.f, 1.f, 1.f}, bv[3] = {0.f, 0.f, 0.f};
+    if constexpr (AFFINE) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            av[c] = a[c];
+            bv[c] = b[c];
+        }
     }
-}
-
-// ---- the same pack with a per-channel affine a_c x_c + b_c in front (torchvision Inception3's transform_input) into a frame WITHOUT a border: the product and
-// the sum in fp32, one rounding.  A channel with a_c = 1 and b_c = 0 is copied as a pattern (-0 and NaN payloads included), so the identity is the plain pack.
-template <bool F16>
-__global__ __launch_bounds__(256) void pack_nchw16_affine_kernel(const unsigned short* __restrict__ x, unsigned short* __restrict__ frame,
-                                                                 const float* __restrict__ a, const float* __restrict__ b, int N, int H, int W, int Wf) {
-    const long long hw = (long long)H * W, total = N * hw;
-    const float av[3] = {a[0], a[1], a[2]}, bv[3] = {b[0], b[1], b[2]};
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < total; q += 256LL * gridDim.x) {
         const long long n_ = q / hw, p = q - n_ * hw;
         const int y = (int)(p / W), xx = (int)(p - (long long)y * W);
         const unsigned short* s = x + n_ * 3 * hw + p;
         u16x4 v{s[0], s[hw], s[2 * hw], 0};
+        if constexpr (AFFINE) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-            if (av[c] != 1.f || bv[c] != 0.f) v[c] = to_h<F16>(av[c] * to_f32<F16>(v[c]) + bv[c]);
-        *reinterpret_cast<u16x4*>(frame + ((n_ * H + y) * Wf + xx) * 4) = v;
+            for (int c = 0; c < 3; ++c)
+                if (av[c] != 1.f || bv[c] != 0.f) v[c] = to_h<F16>(av[c] * to_f32<F16>(v[c]) + bv[c]);
+        }
+        *reinterpret_cast<u16x4*>(frame + ((n_ * (H + 2 * B) + y + B) * Wf + xx + B) * 4) = v;
     }
 }
 
-// torchvision AlexNet's five convolutions (torchvision/models/alexnet.py): the only shapes eegclip_convrelu16 takes
-struct mn_layer { int KS, stride, pad, Cin, Cout; };
-static const mn_layer MN_LAYERS[5] = {{11, 4, 2, 3, 64}, {5, 1, 2, 64, 192}, {3, 1, 1, 192, 384}, {3, 1, 1, 384, 256}, {3, 1, 1, 256, 256}};
-static const mn_layer MN_STEM = {7, 2, 3, 3, 64};            // torchvision ResNet's conv1 (torchvision/models/resnet.py)
-static const mn_layer MN_EFF_STEM = {3, 2, 1, 3, 64};        // torchvision EfficientNet's features.0 (32 filters; rows 32 .. 63 of the packed weight are zero)
+// a convolution's filter as the tile loop sees it
+struct mn_filter { int KH, KW, stride, pad_h, pad_w, Cin, Cout; };
+static mn_filter mn_square(int KS, int stride, int pad, int Cin, int Cout) { return {KS, KS, stride, pad, pad, Cin, Cout}; }
+static bool mn_same(const mn_filter& a, const mn_filter& b) {
+    return a.KH == b.KH && a.KW == b.KW && a.stride == b.stride && a.pad_h == b.pad_h && a.pad_w == b.pad_w && a.Cin == b.Cin && a.Cout == b.Cout;
+}
+
+// the 3-channel first layer of each net -- its padding is the border of the frame the pack writes -- and the smallest image side its entry points take
+enum { MN_ALEXNET, MN_RESNET, MN_EFFNET, MN_INCEPTION };
+struct mn_first { mn_filter F; int min_side; };
+static const mn_first MN_FIRST[4] = {
+    {{11, 11, 4, 2, 2, 3, 64}, 7},     // torchvision AlexNet's features.0
+    {{7, 7, 2, 3, 3, 3, 64}, 1},       // torchvision ResNet's conv1
+    {{3, 3, 2, 1, 1, 3, 64}, 1},       // torchvision EfficientNet's features.0 (32 filters; rows 32 .. 63 of the packed weight are zero)
+    {{3, 3, 2, 0, 0, 3, 64}, 3},       // torchvision Inception3's Conv2d_1a_3x3 (32 filters; rows 32 .. 63 of the packed weight are zero and never stored)
+};
+// torchvision AlexNet's other four convolutions: with features.0 the only shapes eegclip_convrelu16 takes
+static const mn_filter MN_ALEXNET_BODY[4] = {{5, 5, 1, 2, 2, 64, 192}, {3, 3, 1, 1, 1, 192, 384}, {3, 3, 1, 1, 1, 384, 256}, {3, 3, 1, 1, 1, 256, 256}};
 
 // a 3-channel layer's frame width: at least the image and its border, and the 16 pixels of the last window's k-tile; even, so every row starts at 16 bytes
-static int mn_first_width(int Wi, const mn_layer& L) {
-    const int Wo = (Wi + 2 * L.pad - L.KS) / L.stride + 1;
-    int w = L.stride * (Wo - 1) + 16;
-    if (w < Wi + 2 * L.pad) w = Wi + 2 * L.pad;
+static int mn_first_width(int Wi, const mn_filter& F) {
+    const int Wo = (Wi + 2 * F.pad_w - F.KW) / F.stride + 1;
+    int w = F.stride * (Wo - 1) + 16;
+    if (w < Wi + 2 * F.pad_w) w = Wi + 2 * F.pad_w;
     return (w + 1) & ~1;
 }
-static int mn_in_width(int Wi) { return mn_first_width(Wi, MN_LAYERS[0]); }
+static int mn_in_width(int net, int Wi) { return Wi < MN_FIRST[net].min_side ? EEGCLIP_EINVAL : mn_first_width(Wi, MN_FIRST[net].F); }
 
-// what eegclip_convrelu16 and eegclip_convbn16 share: the tile loop's geometry for a layer (0, or EEGCLIP_EINVAL past the kernel's 32-bit offsets) ..
-static int mn_geometry(mn_args& a, const mn_layer& L, int N, int Hi, int Wi, int out_pad) {
-    const int Ho = (Hi + 2 * L.pad - L.KS) / L.stride + 1, Wo = (Wi + 2 * L.pad - L.KS) / L.stride + 1;
-    const bool first = L.Cin == 3;
+static const unsigned short* mn_u16(const void* p) { return static_cast<const unsigned short*>(p); }
+static unsigned short* mn_u16(void* p) { return static_cast<unsigned short*>(p); }
+
+// what the four convolution entry points share: the tile loop's geometry for filter F on a frame with a border of B >= the padding around Hi x Wi images
+// (0, or EEGCLIP_EINVAL past the kernel's 32-bit offsets).  The walk starts at frame pixel (B - pad_h, B - pad_w), so every tap of every window is a frame
+// pixel: a 1 x 1 layer skips whatever border it meets, and a 1 x 7 and a 7 x 1 layer read the same border-3 frame.  A 3-channel layer (B = its padding) reads
+// 4 elements per pixel, one k-tile per ky.  The N tiles cover pad64(Cout) weight rows, 64 nj at a time.
+static int mn_geometry(mn_args& a, const void* in, const mn_filter& F, int N, int Hi, int Wi, int B, int out_pad, int& nj) {
+    const int Ho = (Hi + 2 * F.pad_h - F.KH) / F.stride + 1, Wo = (Wi + 2 * F.pad_w - F.KW) / F.stride + 1;
+    const bool first = F.Cin == 3;
     a.Ho = Ho; a.Wo = Wo;
-    a.Hp = Hi + 2 * L.pad;                                   // (the frame's border IS the layer's padding: every tap of every window is a frame pixel)
-    a.Wp = first ? mn_first_width(Wi, L) : Wi + 2 * L.pad;
-    a.pix = first ? 4 : L.Cin;
-    a.Hop = Ho + 2 * out_pad; a.Wop = Wo + 2 * out_pad; a.opad = out_pad; a.Cout = L.Cout;
-    a.KH = L.KS; a.KW = first ? 1 : L.KS; a.kc = first ? MN_K : L.Cin; a.stride = L.stride;
+    a.Hp = Hi + 2 * B;
+    a.Wp = first ? mn_first_width(Wi, F) : Wi + 2 * B;
+    a.pix = first ? 4 : F.Cin;
+    a.Hop = Ho + 2 * out_pad; a.Wop = Wo + 2 * out_pad; a.opad = out_pad; a.Cout = F.Cout;
+    a.KH = F.KH; a.KW = first ? 1 : F.KW; a.kc = first ? MN_K : F.Cin; a.stride = F.stride;
     const long long M = (long long)N * Ho * Wo;
     // (the kernel's element offsets into the input frame are 32-bit)
     if (M > 0x7fffffffLL || (long long)N * a.Hp * a.Wp * a.pix > 0x7fffffffLL) return EEGCLIP_EINVAL;
     a.M = (int)M;
-    const int nj = L.Cout % 128 == 0 ? 2 : 1;
-    a.tiles_n = L.Cout / (64 * nj);
+    const int cpad = (F.Cout + 63) / 64 * 64;
+    nj = cpad % 128 == 0 ? 2 : 1;
+    a.tiles_n = cpad / (64 * nj);
     a.ntiles = a.tiles_n * ((a.M + MN_T - 1) / MN_T);
     a.chunk = (a.ntiles + 7) / 8;
+    a.in = mn_u16(in) + ((long long)(B - F.pad_h) * a.Wp + (B - F.pad_w)) * a.pix;
     return 0;
 }
 
 // .. and the launch, N tiles of 64 nj channels
 template <class ARGS>
-static int mn_launch_nj(const ARGS& a, int nj, int dtype, void* stream) {
+static int mn_launch(const ARGS& a, int nj, int dtype, void* stream) {
     const size_t lds = 2 * (size_t)(MN_A_B + 64 * nj * MN_ROWB);
     const dim3 grid((unsigned)(8 * a.chunk)), block(512);
     const bool f16 = dtype == EEGCLIP_DT_F16;
@@ -500,111 +501,124 @@ static int mn_launch_nj(const ARGS& a, int nj, int dtype, void* stream) {
     return (int)hipGetLastError();
 }
 
-template <class ARGS>
-static int mn_launch(const ARGS& a, int dtype, void* stream) {
-    return mn_launch_nj(a, a.Cout % 128 == 0 ? 2 : 1, dtype, stream);
-}
-
 static unsigned mn_grid(long long threads) {
     const long long g = (threads + 255) / 256;
     return (unsigned)(g > 16384 ? 16384 : g);
+}
+
+// the launch of an elementwise kernel<F16> over `threads` grid-stride threads, in the dtype's instantiation
+#define MN_ELEMENTWISE(kernel, dtype, threads, stream, ...)                                                                        \
+    do {                                                                                                                           \
+        const dim3 grid_(mn_grid(threads));                                                                                        \
+        if ((dtype) == EEGCLIP_DT_F16) EEG_LAUNCH((kernel<true>), grid_, dim3(256), 0, stream, __VA_ARGS__);                       \
+        else                           EEG_LAUNCH((kernel<false>), grid_, dim3(256), 0, stream, __VA_ARGS__);                      \
+    } while (0)
+
+// the four packs: net's first layer gives the frame's border and width; a, b = NULL without an affine
+static int mn_pack(int net, const void* x, void* frame, bool affine, const float* a, const float* b, int N, int H, int W, int dtype, void* stream) {
+    const mn_first& L = MN_FIRST[net];
+    if (!x || !frame || (affine && (!a || !b)) || N < 1 || H < L.min_side || W < L.min_side || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(x) & 1u) || (reinterpret_cast<uintptr_t>(frame) & 15u)) return EEGCLIP_EALIGN;
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3u) return EEGCLIP_EALIGN;
+    const dim3 grid(mn_grid((long long)N * H * W)), block(256);
+    const int Wf = mn_first_width(W, L.F), B = L.F.pad_h;
+    if (!affine)                         EEG_LAUNCH((pack_nchw16_kernel<false, false>), grid, block, 0, stream, mn_u16(x), mn_u16(frame), a, b, N, H, W, Wf, B);
+    else if (dtype == EEGCLIP_DT_F16)    EEG_LAUNCH((pack_nchw16_kernel<true, true>), grid, block, 0, stream, mn_u16(x), mn_u16(frame), a, b, N, H, W, Wf, B);
+    else                                 EEG_LAUNCH((pack_nchw16_kernel<true, false>), grid, block, 0, stream, mn_u16(x), mn_u16(frame), a, b, N, H, W, Wf, B);
+    return (int)hipGetLastError();
+}
+
+// MaxPool2d(3, 2) of a channel slice; the callers have checked their own limits
+static int mn_maxpool(const void* in, void* out, int N, int H, int W, int C, int istride, int ipad, int ostride, int oc0, int opad, int dtype, void* stream) {
+    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) return EEGCLIP_EALIGN;
+    const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
+    MN_ELEMENTWISE(maxpool16_kernel, dtype, (long long)N * Ho * Wo * (C / 8), stream, mn_u16(in), mn_u16(out), N, H, W, C, istride, ipad, ostride, oc0, opad, Ho,
+                   Wo);
+    return (int)hipGetLastError();
 }
 
 }  // namespace eeg
 
 using namespace eeg;
 
-extern "C" int eegclip_convrelu16_in_width(int Wi) { return Wi < 7 ? EEGCLIP_EINVAL : mn_in_width(Wi); }
+extern "C" int eegclip_convrelu16_in_width(int Wi) { return mn_in_width(MN_ALEXNET, Wi); }
 
 extern "C" int eegclip_convrelu16(const eegclip_convrelu16_desc* d, void* stream) {
     if (!d || !d->in || !d->W || !d->bias || !d->out || d->N < 1 || d->Hi < 1 || d->Wi < 1 || d->out_pad < 0 || d->out_pad > 2 || !half_dtype_ok(d->dtype))
         return EEGCLIP_EINVAL;
-    const mn_layer* L = nullptr;
-    for (const mn_layer& l : MN_LAYERS)
-        if (l.KS == d->KS && l.stride == d->stride && l.pad == d->pad && l.Cin == d->Cin && l.Cout == d->Cout) L = &l;
-    if (!L || d->Hi + 2 * L->pad < L->KS || d->Wi + 2 * L->pad < L->KS) return EEGCLIP_EINVAL;
+    const mn_filter F = mn_square(d->KS, d->stride, d->pad, d->Cin, d->Cout);
+    bool known = mn_same(F, MN_FIRST[MN_ALEXNET].F);
+    for (const mn_filter& l : MN_ALEXNET_BODY) known = known || mn_same(F, l);
+    if (!known || d->Hi + 2 * F.pad_h < F.KH || d->Wi + 2 * F.pad_w < F.KW) return EEGCLIP_EINVAL;
     mn_args a;
-    a.in = static_cast<const unsigned short*>(d->in);
-    a.W = static_cast<const unsigned short*>(d->W);
-    a.bias = static_cast<const unsigned short*>(d->bias);
-    a.out = static_cast<unsigned short*>(d->out);
-    if (mn_geometry(a, *L, d->N, d->Hi, d->Wi, d->out_pad)) return EEGCLIP_EINVAL;
+    int nj;
+    a.W = mn_u16(d->W);
+    a.bias = mn_u16(d->bias);
+    a.out = mn_u16(d->out);
+    if (mn_geometry(a, d->in, F, d->N, d->Hi, d->Wi, d->pad, d->out_pad, nj)) return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d->in) | reinterpret_cast<uintptr_t>(d->W)) & 15u) return EEGCLIP_EALIGN;
     if ((reinterpret_cast<uintptr_t>(d->out) | reinterpret_cast<uintptr_t>(d->bias)) & 7u) return EEGCLIP_EALIGN;
-    return mn_launch(a, d->dtype, stream);
+    return mn_launch(a, nj, d->dtype, stream);
 }
 
-extern "C" int eegclip_convbn16_in_width(int Wi) { return Wi < 1 ? EEGCLIP_EINVAL : mn_first_width(Wi, MN_STEM); }
+extern "C" int eegclip_convbn16_in_width(int Wi) { return mn_in_width(MN_RESNET, Wi); }
 
 extern "C" int eegclip_convbn16(const eegclip_convbn16_desc* d, void* stream) {
     if (!d || !d->in || !d->W || !d->scale || !d->shift || !d->out || d->N < 1 || d->Hi < 1 || d->Wi < 1 || d->out_pad < 0 || d->out_pad > 2 ||
         (d->relu != 0 && d->relu != 1) || !half_dtype_ok(d->dtype))
         return EEGCLIP_EINVAL;
-    mn_layer L = {d->KS, d->stride, d->pad, d->Cin, d->Cout};
-    const bool stem = L.KS == MN_STEM.KS && L.stride == MN_STEM.stride && L.pad == MN_STEM.pad && L.Cin == MN_STEM.Cin && L.Cout == MN_STEM.Cout;
-    const bool body = (L.KS == 1 || L.KS == 3) && (L.stride == 1 || L.stride == 2) && L.pad == L.KS / 2 && L.Cin >= 64 && L.Cin % 64 == 0 && L.Cout >= 64 &&
-                      L.Cout % 64 == 0;
+    const mn_filter F = mn_square(d->KS, d->stride, d->pad, d->Cin, d->Cout);
+    const bool stem = mn_same(F, MN_FIRST[MN_RESNET].F);
+    const bool body = (d->KS == 1 || d->KS == 3) && (d->stride == 1 || d->stride == 2) && d->pad == d->KS / 2 && d->Cin >= 64 && d->Cin % 64 == 0 && d->Cout >= 64 &&
+                      d->Cout % 64 == 0;
     if (!stem && !body) return EEGCLIP_EINVAL;
     mn_bn_args a;
-    a.in = static_cast<const unsigned short*>(d->in);
-    a.W = static_cast<const unsigned short*>(d->W);
+    int nj;
+    a.W = mn_u16(d->W);
     a.bias = nullptr;
-    a.out = static_cast<unsigned short*>(d->out);
+    a.out = mn_u16(d->out);
     a.scale = static_cast<const float*>(d->scale);
     a.shift = static_cast<const float*>(d->shift);
-    a.residual = static_cast<const unsigned short*>(d->residual);
+    a.residual = mn_u16(d->residual);
     a.relu = d->relu;
-    if (mn_geometry(a, L, d->N, d->Hi, d->Wi, d->out_pad)) return EEGCLIP_EINVAL;
+    if (mn_geometry(a, d->in, F, d->N, d->Hi, d->Wi, d->pad, d->out_pad, nj)) return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d->in) | reinterpret_cast<uintptr_t>(d->W)) & 15u) return EEGCLIP_EALIGN;
     if ((reinterpret_cast<uintptr_t>(d->out) | reinterpret_cast<uintptr_t>(d->residual)) & 7u) return EEGCLIP_EALIGN;
     if ((reinterpret_cast<uintptr_t>(d->scale) | reinterpret_cast<uintptr_t>(d->shift)) & 3u) return EEGCLIP_EALIGN;
-    return mn_launch(a, d->dtype, stream);
+    return mn_launch(a, nj, d->dtype, stream);
 }
 
-extern "C" int eegclip_convbnact16_in_width(int Wi) { return Wi < 1 ? EEGCLIP_EINVAL : mn_first_width(Wi, MN_EFF_STEM); }
+extern "C" int eegclip_convbnact16_in_width(int Wi) { return mn_in_width(MN_EFFNET, Wi); }
 
 extern "C" int eegclip_convbnact16(const eegclip_convbnact16_desc* d, void* stream) {
     if (!d || !d->in || !d->W || !d->scale || !d->shift || !d->out || d->N < 1 || d->Hi < 1 || d->Wi < 1 || d->out_pad < 0 || d->out_pad > 2 || d->in_pad < 0 ||
         d->in_pad > 2 || d->act < 0 || d->act > 2 || !half_dtype_ok(d->dtype))
         return EEGCLIP_EINVAL;
-    const mn_layer L = {d->KS, d->stride, d->pad, d->Cin, d->Cout};
-    const bool stem = L.KS == MN_EFF_STEM.KS && L.stride == MN_EFF_STEM.stride && L.pad == MN_EFF_STEM.pad && L.Cin == MN_EFF_STEM.Cin &&
-                      L.Cout == MN_EFF_STEM.Cout && d->in_pad == 0;
-    const bool point = L.KS == 1 && L.stride == 1 && L.pad == 0 && L.Cin >= 64 && L.Cin % 64 == 0 && L.Cout >= 64 && L.Cout % 64 == 0;
+    const mn_filter F = mn_square(d->KS, d->stride, d->pad, d->Cin, d->Cout);
+    const bool stem = mn_same(F, MN_FIRST[MN_EFFNET].F) && d->in_pad == 0;
+    const bool point = d->KS == 1 && d->stride == 1 && d->pad == 0 && d->Cin >= 64 && d->Cin % 64 == 0 && d->Cout >= 64 && d->Cout % 64 == 0;
     if (!stem && !point) return EEGCLIP_EINVAL;
     mn_act_args a;
-    a.W = static_cast<const unsigned short*>(d->W);
+    int nj;
+    a.W = mn_u16(d->W);
     a.bias = nullptr;
-    a.out = static_cast<unsigned short*>(d->out);
+    a.out = mn_u16(d->out);
     a.scale = static_cast<const float*>(d->scale);
     a.shift = static_cast<const float*>(d->shift);
-    a.residual = static_cast<const unsigned short*>(d->residual);
+    a.residual = mn_u16(d->residual);
     a.act = d->act;
-    if (mn_geometry(a, L, d->N, d->Hi, d->Wi, d->out_pad)) return EEGCLIP_EINVAL;
-    // a 1 x 1 layer may read the interior of a frame with a border (the depthwise layer in front of it needed one): the tile loop walks the wider frame from
-    // its pixel (in_pad, in_pad)
-    a.Hp += 2 * d->in_pad;
-    a.Wp += 2 * d->in_pad;
-    if ((long long)d->N * a.Hp * a.Wp * a.pix > 0x7fffffffLL) return EEGCLIP_EINVAL;
-    a.in = static_cast<const unsigned short*>(d->in) + ((long long)d->in_pad * a.Wp + d->in_pad) * a.pix;
+    // a 1 x 1 layer may read the interior of a frame with a border (the depthwise layer in front of it needed one)
+    if (mn_geometry(a, d->in, F, d->N, d->Hi, d->Wi, d->pad + d->in_pad, d->out_pad, nj)) return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d->in) | reinterpret_cast<uintptr_t>(d->W)) & 15u) return EEGCLIP_EALIGN;
     if ((reinterpret_cast<uintptr_t>(d->out) | reinterpret_cast<uintptr_t>(d->residual)) & 7u) return EEGCLIP_EALIGN;
     if ((reinterpret_cast<uintptr_t>(d->scale) | reinterpret_cast<uintptr_t>(d->shift)) & 3u) return EEGCLIP_EALIGN;
-    return mn_launch(a, d->dtype, stream);
+    return mn_launch(a, nj, d->dtype, stream);
 }
 
 extern "C" int eegclip_maxpool16(const void* in, void* out, int N, int H, int W, int C, int in_pad, int out_pad, int dtype, void* stream) {
     if (!in || !out || N < 1 || H < 3 || W < 3 || C < 8 || C % 8 || in_pad < 0 || in_pad > 2 || out_pad < 0 || out_pad > 2 || !half_dtype_ok(dtype))
         return EEGCLIP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) return EEGCLIP_EALIGN;
-    const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
-    long long g = ((long long)N * Ho * Wo * (C / 8) + 255) / 256;
-    if (g > 16384) g = 16384;
-    const unsigned short* i16 = static_cast<const unsigned short*>(in);
-    unsigned short* o16 = static_cast<unsigned short*>(out);
-    if (dtype == EEGCLIP_DT_F16) EEG_LAUNCH((maxpool16_kernel<true>), dim3((unsigned)g), dim3(256), 0, stream, i16, o16, N, H, W, C, in_pad, out_pad, Ho, Wo);
-    else                         EEG_LAUNCH((maxpool16_kernel<false>), dim3((unsigned)g), dim3(256), 0, stream, i16, o16, N, H, W, C, in_pad, out_pad, Ho, Wo);
-    return (int)hipGetLastError();
+    return mn_maxpool(in, out, N, H, W, C, C, in_pad, C, 0, out_pad, dtype, stream);
 }
 
 extern "C" int eegclip_maxpool16_pad(const void* in, void* out, int N, int H, int W, int C, int in_pad, int out_pad, int dtype, void* stream) {
@@ -612,21 +626,14 @@ extern "C" int eegclip_maxpool16_pad(const void* in, void* out, int N, int H, in
         return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) return EEGCLIP_EALIGN;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const dim3 grid(mn_grid((long long)N * Ho * Wo * (C / 8)));
-    const unsigned short* i16 = static_cast<const unsigned short*>(in);
-    unsigned short* o16 = static_cast<unsigned short*>(out);
-    if (dtype == EEGCLIP_DT_F16) EEG_LAUNCH((maxpool16_pad_kernel<true>), grid, dim3(256), 0, stream, i16, o16, N, H, W, C, in_pad, out_pad, Ho, Wo);
-    else                         EEG_LAUNCH((maxpool16_pad_kernel<false>), grid, dim3(256), 0, stream, i16, o16, N, H, W, C, in_pad, out_pad, Ho, Wo);
+    MN_ELEMENTWISE(maxpool16_pad_kernel, dtype, (long long)N * Ho * Wo * (C / 8), stream, mn_u16(in), mn_u16(out), N, H, W, C, in_pad, out_pad, Ho, Wo);
     return (int)hipGetLastError();
 }
 
 extern "C" int eegclip_avgpool16(const void* in, float* out, int N, int H, int W, int C, int dtype, void* stream) {
     if (!in || !out || N < 1 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL || C < 8 || C % 8 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(in) & 15u) || (reinterpret_cast<uintptr_t>(out) & 3u)) return EEGCLIP_EALIGN;
-    const dim3 grid(mn_grid((long long)N * (C / 8)));
-    const unsigned short* i16 = static_cast<const unsigned short*>(in);
-    if (dtype == EEGCLIP_DT_F16) EEG_LAUNCH((avgpool16_kernel<true>), grid, dim3(256), 0, stream, i16, out, N, H * W, C);
-    else                         EEG_LAUNCH((avgpool16_kernel<false>), grid, dim3(256), 0, stream, i16, out, N, H * W, C);
+    MN_ELEMENTWISE(avgpool16_kernel, dtype, (long long)N * (C / 8), stream, mn_u16(in), out, N, H * W, C);
     return (int)hipGetLastError();
 }
 
@@ -638,33 +645,23 @@ extern "C" int eegclip_corr_distance(const float* a, const float* b, int N, int 
 }
 
 extern "C" int eegclip_pack_nchw16(const void* x, void* frame, int N, int H, int W, int dtype, void* stream) {
-    if (!x || !frame || N < 1 || H < 7 || W < 7 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(x) & 1u) || (reinterpret_cast<uintptr_t>(frame) & 15u)) return EEGCLIP_EALIGN;
-    EEG_LAUNCH((pack_nchw16_kernel<2>), dim3(mn_grid((long long)N * H * W)), dim3(256), 0, stream, static_cast<const unsigned short*>(x),
-               static_cast<unsigned short*>(frame), N, H, W, mn_in_width(W));
-    return (int)hipGetLastError();
+    return mn_pack(MN_ALEXNET, x, frame, false, nullptr, nullptr, N, H, W, dtype, stream);
 }
 
 extern "C" int eegclip_pack_nchw16_stem(const void* x, void* frame, int N, int H, int W, int dtype, void* stream) {
-    if (!x || !frame || N < 1 || H < 1 || W < 1 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(x) & 1u) || (reinterpret_cast<uintptr_t>(frame) & 15u)) return EEGCLIP_EALIGN;
-    EEG_LAUNCH((pack_nchw16_kernel<3>), dim3(mn_grid((long long)N * H * W)), dim3(256), 0, stream, static_cast<const unsigned short*>(x),
-               static_cast<unsigned short*>(frame), N, H, W, mn_first_width(W, MN_STEM));
-    return (int)hipGetLastError();
+    return mn_pack(MN_RESNET, x, frame, false, nullptr, nullptr, N, H, W, dtype, stream);
 }
 
 extern "C" int eegclip_pack_nchw16_pad1(const void* x, void* frame, int N, int H, int W, int dtype, void* stream) {
-    if (!x || !frame || N < 1 || H < 1 || W < 1 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(x) & 1u) || (reinterpret_cast<uintptr_t>(frame) & 15u)) return EEGCLIP_EALIGN;
-    EEG_LAUNCH((pack_nchw16_kernel<1>), dim3(mn_grid((long long)N * H * W)), dim3(256), 0, stream, static_cast<const unsigned short*>(x),
-               static_cast<unsigned short*>(frame), N, H, W, mn_first_width(W, MN_EFF_STEM));
-    return (int)hipGetLastError();
+    return mn_pack(MN_EFFNET, x, frame, false, nullptr, nullptr, N, H, W, dtype, stream);
+}
+
+extern "C" int eegclip_pack_nchw16_affine(const void* x, void* frame, const float* a, const float* b, int N, int H, int W, int dtype, void* stream) {
+    return mn_pack(MN_INCEPTION, x, frame, true, a, b, N, H, W, dtype, stream);
 }
 
 // ---- the Inception row (torchvision/models/inception.py): convolution + BatchNorm + ReLU into a channel slice of a concatenated frame
-static const mn_layer MN_INC_STEM = {3, 2, 0, 3, 64};        // Conv2d_1a_3x3 (32 filters; rows 32 .. 63 of the packed weight are zero and never stored)
-
-extern "C" int eegclip_convbncat16_in_width(int Wi) { return Wi < 3 ? EEGCLIP_EINVAL : mn_first_width(Wi, MN_INC_STEM); }
+extern "C" int eegclip_convbncat16_in_width(int Wi) { return mn_in_width(MN_INCEPTION, Wi); }
 
 extern "C" int eegclip_convbncat16(const eegclip_convbncat16_desc* d, void* stream) {
     if (!d || !d->in || !d->W || !d->scale || !d->shift || !d->out || d->N < 1 || d->Hi < 1 || d->Wi < 1 || d->out_pad < 0 || d->out_pad > 3 || d->in_pad < 0 ||
@@ -678,47 +675,29 @@ extern "C" int eegclip_convbncat16(const eegclip_convbncat16_desc* d, void* stre
         shape = ph == KH / 2 && pw == KW / 2 && d->stride == 1;
     if (!shape || d->Cout < 8 || d->Cout % 8 || d->out_c0 < 0 || d->out_c0 % 8 || d->out_stride % 8 || (long long)d->out_c0 + d->Cout > d->out_stride)
         return EEGCLIP_EINVAL;
-    const bool first = d->Cin == 3;
-    if (first ? !(KH == 3 && d->stride == 2 && d->in_pad == 0 && d->Cout <= 64) : (d->Cin < 64 || d->Cin % 64 || d->in_pad < (ph > pw ? ph : pw)))
+    if (d->Cin == 3 ? !(KH == 3 && d->stride == 2 && d->in_pad == 0 && d->Cout <= 64) : (d->Cin < 64 || d->Cin % 64 || d->in_pad < (ph > pw ? ph : pw)))
         return EEGCLIP_EINVAL;
     if (d->Hi + 2 * ph < KH || d->Wi + 2 * pw < KW) return EEGCLIP_EINVAL;
     mn_cat_args a;
-    a.W = static_cast<const unsigned short*>(d->W);
+    int nj;
+    a.W = mn_u16(d->W);
     a.bias = nullptr;
-    a.out = static_cast<unsigned short*>(d->out);
+    a.out = mn_u16(d->out);
     a.scale = static_cast<const float*>(d->scale);
     a.shift = static_cast<const float*>(d->shift);
     a.relu = d->relu; a.ostride = d->out_stride; a.oc0 = d->out_c0;
-    const int Ho = (d->Hi + 2 * ph - KH) / d->stride + 1, Wo = (d->Wi + 2 * pw - KW) / d->stride + 1;
-    a.Ho = Ho; a.Wo = Wo;
-    a.Hp = d->Hi + 2 * d->in_pad;
-    a.Wp = first ? mn_first_width(d->Wi, MN_INC_STEM) : d->Wi + 2 * d->in_pad;
-    a.pix = first ? 4 : d->Cin;
-    a.Hop = Ho + 2 * d->out_pad; a.Wop = Wo + 2 * d->out_pad; a.opad = d->out_pad; a.Cout = d->Cout;
-    a.KH = KH; a.KW = first ? 1 : KW; a.kc = first ? MN_K : d->Cin; a.stride = d->stride;
-    const long long M = (long long)d->N * Ho * Wo;
-    if (M > 0x7fffffffLL || (long long)d->N * a.Hp * a.Wp * a.pix > 0x7fffffffLL) return EEGCLIP_EINVAL;
-    a.M = (int)M;
-    const int cpad = (d->Cout + 63) / 64 * 64, nj = cpad % 128 == 0 ? 2 : 1;
-    a.tiles_n = cpad / (64 * nj);
-    a.ntiles = a.tiles_n * ((a.M + MN_T - 1) / MN_T);
-    a.chunk = (a.ntiles + 7) / 8;
-    // the tile loop walks the frame from its pixel (in_pad - pad_h, in_pad - pad_w): a 1 x 7 and a 7 x 1 layer read the same border-3 frame
-    a.in = static_cast<const unsigned short*>(d->in) + ((long long)(d->in_pad - ph) * a.Wp + (d->in_pad - pw)) * a.pix;
+    // (Cout is the layer's own count: the epilogue stores the channel groups below it)
+    if (mn_geometry(a, d->in, {KH, KW, d->stride, ph, pw, d->Cin, d->Cout}, d->N, d->Hi, d->Wi, d->in_pad, d->out_pad, nj)) return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(d->in) | reinterpret_cast<uintptr_t>(d->W)) & 15u) return EEGCLIP_EALIGN;
     if (reinterpret_cast<uintptr_t>(d->out) & 7u) return EEGCLIP_EALIGN;
     if ((reinterpret_cast<uintptr_t>(d->scale) | reinterpret_cast<uintptr_t>(d->shift)) & 3u) return EEGCLIP_EALIGN;
-    return mn_launch_nj(a, nj, d->dtype, stream);
+    return mn_launch(a, nj, d->dtype, stream);
 }
 
 extern "C" int eegclip_avgpool3x3_16(const void* in, void* out, int N, int H, int W, int C, int in_pad, int dtype, void* stream) {
     if (!in || !out || N < 1 || H < 1 || W < 1 || C < 8 || C % 8 || in_pad < 1 || in_pad > 3 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) return EEGCLIP_EALIGN;
-    const dim3 grid(mn_grid((long long)N * H * W * (C / 8)));
-    const unsigned short* i16 = static_cast<const unsigned short*>(in);
-    unsigned short* o16 = static_cast<unsigned short*>(out);
-    if (dtype == EEGCLIP_DT_F16) EEG_LAUNCH((avgpool3x3_16_kernel<true>), grid, dim3(256), 0, stream, i16, o16, N, H, W, C, in_pad);
-    else                         EEG_LAUNCH((avgpool3x3_16_kernel<false>), grid, dim3(256), 0, stream, i16, o16, N, H, W, C, in_pad);
+    MN_ELEMENTWISE(avgpool3x3_16_kernel, dtype, (long long)N * H * W * (C / 8), stream, mn_u16(in), mn_u16(out), N, H, W, C, in_pad);
     return (int)hipGetLastError();
 }
 
@@ -727,27 +706,5 @@ extern "C" int eegclip_maxpool16_cat(const void* in, void* out, int N, int H, in
     if (!in || !out || N < 1 || H < 3 || W < 3 || C < 8 || C % 8 || in_stride < C || in_stride % 8 || out_c0 < 0 || out_c0 % 8 || out_stride % 8 ||
         (long long)out_c0 + C > out_stride || in_pad < 0 || in_pad > 3 || out_pad < 0 || out_pad > 3 || !half_dtype_ok(dtype))
         return EEGCLIP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) return EEGCLIP_EALIGN;
-    const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
-    const dim3 grid(mn_grid((long long)N * Ho * Wo * (C / 8)));
-    const unsigned short* i16 = static_cast<const unsigned short*>(in);
-    unsigned short* o16 = static_cast<unsigned short*>(out);
-    if (dtype == EEGCLIP_DT_F16)
-        EEG_LAUNCH((maxpool16_cat_kernel<true>), grid, dim3(256), 0, stream, i16, o16, N, H, W, C, in_stride, in_pad, out_stride, out_c0, out_pad, Ho, Wo);
-    else
-        EEG_LAUNCH((maxpool16_cat_kernel<false>), grid, dim3(256), 0, stream, i16, o16, N, H, W, C, in_stride, in_pad, out_stride, out_c0, out_pad, Ho, Wo);
-    return (int)hipGetLastError();
-}
-
-extern "C" int eegclip_pack_nchw16_affine(const void* x, void* frame, const float* a, const float* b, int N, int H, int W, int dtype, void* stream) {
-    if (!x || !frame || !a || !b || N < 1 || H < 3 || W < 3 || !half_dtype_ok(dtype)) return EEGCLIP_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(x) & 1u) || (reinterpret_cast<uintptr_t>(frame) & 15u)) return EEGCLIP_EALIGN;
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3u) return EEGCLIP_EALIGN;
-    const dim3 grid(mn_grid((long long)N * H * W));
-    const unsigned short* x16 = static_cast<const unsigned short*>(x);
-    unsigned short* f16 = static_cast<unsigned short*>(frame);
-    const int wf = mn_first_width(W, MN_INC_STEM);
-    if (dtype == EEGCLIP_DT_F16) EEG_LAUNCH((pack_nchw16_affine_kernel<true>), grid, dim3(256), 0, stream, x16, f16, a, b, N, H, W, wf);
-    else                         EEG_LAUNCH((pack_nchw16_affine_kernel<false>), grid, dim3(256), 0, stream, x16, f16, a, b, N, H, W, wf);
-    return (int)hipGetLastError();
+    return mn_maxpool(in, out, N, H, W, C, in_stride, in_pad, out_stride, out_c0, out_pad, dtype, stream);
 }

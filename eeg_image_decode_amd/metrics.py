@@ -122,16 +122,22 @@ def clip_two_way(images, recons, tower, size=224, **kw):
     return two_way_identification(feats[0], feats[1], **kw)
 
 
+def _features(images, recons, net, pre, size):
+    """net's output for both sides, each through the row's preprocess.*_preprocess `pre` at `size`, float tensors as values in [0, 1]"""
+    feats = []
+    for x in (images, recons):
+        kw = {"in_range": (0.0, 1.0)} if isinstance(x, torch.Tensor) and x.is_floating_point() else {}
+        feats.append(net(pre(x, size=size, dtype=net.dtype, device=net.device, **kw)))
+    return feats
+
+
 def alexnet_two_way(images, recons, net, size=256, return_counts=False):
     """the notebooks' AlexNet(2) and AlexNet(5) rows: {"AlexNet(2)": score, "AlexNet(5)": score}, two-way identification on `features.4` and `features.11` of
     `net` (a metric_nets.AlexNetFeatures; with torchvision's IMAGENET1K_V1 weights loaded, the notebooks' net).  Both sides go through
     preprocess.alexnet_preprocess(size) -- float tensors as values in [0, 1] -- and ONE forward each gives both nodes.  return_counts=True: each entry is
     (score, count (N,) int32 on the device)."""
-    feats = []
-    for x in (images, recons):
-        kw = {"in_range": (0.0, 1.0)} if isinstance(x, torch.Tensor) and x.is_floating_point() else {}
-        feats.append(net(preprocess.alexnet_preprocess(x, size=size, dtype=net.dtype, device=net.device, **kw)))
-    return {row: two_way_identification(feats[0][node], feats[1][node], return_counts=return_counts)
+    real, recon = _features(images, recons, net, preprocess.alexnet_preprocess, size)
+    return {row: two_way_identification(real[node], recon[node], return_counts=return_counts)
             for row, node in (("AlexNet(2)", "features.4"), ("AlexNet(5)", "features.11"))}
 
 
@@ -152,41 +158,31 @@ def correlation_distance(real_feats, recon_feats):
     return out
 
 
+def _distance_row(images, recons, net, pre, size, return_distances):
+    d = correlation_distance(*_features(images, recons, net, pre, size))
+    mean = float(d.mean())
+    return (mean, d) if return_distances else mean
+
+
 def swav_distance(images, recons, net, size=224, return_distances=False):
     """the notebooks' SwAV row: the mean over the pairs of scipy's correlation distance between the `avgpool` features of `net` (a metric_nets.ResNetFeatures;
     swav_resnet50 with the SwAV checkpoint loaded is the notebooks' net) -- lower is better.  Both sides go through preprocess.swav_preprocess(size), float
     tensors as values in [0, 1].  return_distances=True: (mean, distances (N,) fp32 on the device)."""
-    feats = []
-    for x in (images, recons):
-        kw = {"in_range": (0.0, 1.0)} if isinstance(x, torch.Tensor) and x.is_floating_point() else {}
-        feats.append(net(preprocess.swav_preprocess(x, size=size, dtype=net.dtype, device=net.device, **kw)))
-    d = correlation_distance(feats[0], feats[1])
-    mean = float(d.mean())
-    return (mean, d) if return_distances else mean
+    return _distance_row(images, recons, net, preprocess.swav_preprocess, size, return_distances)
 
 
 def effnet_distance(images, recons, net, size=255, return_distances=False):
     """the notebooks' EffNet-B row: the mean over the pairs of scipy's correlation distance between the `avgpool` features of `net` (a
     metric_nets.EfficientNetFeatures; efficientnet_b1 with torchvision's weights loaded is the notebooks' net) -- lower is better.  Both sides go through
     preprocess.effnet_preprocess(size), float tensors as values in [0, 1].  return_distances=True: (mean, distances (N,) fp32 on the device)."""
-    feats = []
-    for x in (images, recons):
-        kw = {"in_range": (0.0, 1.0)} if isinstance(x, torch.Tensor) and x.is_floating_point() else {}
-        feats.append(net(preprocess.effnet_preprocess(x, size=size, dtype=net.dtype, device=net.device, **kw)))
-    d = correlation_distance(feats[0], feats[1])
-    mean = float(d.mean())
-    return (mean, d) if return_distances else mean
+    return _distance_row(images, recons, net, preprocess.effnet_preprocess, size, return_distances)
 
 
 def inception_two_way(images, recons, net, size=342, return_counts=False):
     """the notebooks' Inception row: two-way identification on the `avgpool` features (N, 2048) of `net` (a metric_nets.InceptionFeatures; inception_v3 with
     torchvision's weights loaded is the notebooks' net).  Both sides go through preprocess.inception_preprocess(size), float tensors as values in [0, 1].
     return_counts=True: (score, count (N,) int32 on the device)."""
-    feats = []
-    for x in (images, recons):
-        kw = {"in_range": (0.0, 1.0)} if isinstance(x, torch.Tensor) and x.is_floating_point() else {}
-        feats.append(net(preprocess.inception_preprocess(x, size=size, dtype=net.dtype, device=net.device, **kw)))
-    return two_way_identification(feats[0], feats[1], return_counts=return_counts)
+    return two_way_identification(*_features(images, recons, net, preprocess.inception_preprocess, size), return_counts=return_counts)
 
 
 def reconstruction_metrics(images, recons, feature_nets=None, size=425, device=None, alexnet=None, swav=None, effnet=None, inception=None):

@@ -10,9 +10,10 @@ import torch
 
 import inception_ref as R
 import metric_nets_ref as MR
+import net_cases as C
 import recon_metrics_ref as RM
+from net_cases import MARGIN
 
-MARGIN = 2.0
 FULL, SHALLOW = R.FULL, (1, 1, 1)
 CAT, AVG3, MAXCAT = "eegclip_convbncat16", "eegclip_avgpool3x3_16", "eegclip_maxpool16_cat"
 ROW_NOISE = 0.3                                # MR.mixed_pairs' noise for the row (two_way_inputs)
@@ -32,35 +33,12 @@ def net_and_refs(device, H, W, N, dtype, blocks):
 
 
 def launches(net, x, **kw):
-    """-> (the C-ABI launches of one forward, in order, seen through a proxy in front of the library (metric_nets fetches it per call); per eegclip_convbncat16
-    its descriptor's (KH, KW, stride, pad_h, pad_w, Cout) and (out, out_c0, Cout, out_stride), per eegclip_maxpool16_cat (out, out_c0, C, out_stride); the result)"""
-    import eeg_image_decode_amd.metric_nets as MN
-    real, seen, convs, slices = MN.lib, [], [], []
-
-    class Recording:
-        def __getattr__(self, name):
-            fn = getattr(real(), name)
-            if name == "eegclip_convbncat16_in_width":           # (host arithmetic, no launch)
-                return fn
-            seen.append(name)
-            if name == CAT:
-                def conv(d, stream):
-                    convs.append((d.KH, d.KW, d.stride, d.pad_h, d.pad_w, d.Cout))
-                    slices.append((d.out, d.out_c0, d.Cout, d.out_stride))
-                    return fn(d, stream)
-                return conv
-            if name == MAXCAT:
-                def pool(*a):
-                    slices.append((a[1], a[9], a[5], a[8]))
-                    return fn(*a)
-                return pool
-            return fn
-    MN.lib = lambda: Recording()
-    try:
-        out = net(x, **kw)
-    finally:
-        MN.lib = real
-    return seen, convs, slices, out
+    """-> (the C-ABI launches of one forward, in order; per eegclip_convbncat16 its descriptor's (KH, KW, stride, pad_h, pad_w, Cout); per eegclip_convbncat16
+    (out, out_c0, Cout, out_stride) and per eegclip_maxpool16_cat (out, out_c0, C, out_stride), in launch order; the result)"""
+    seen, rec, out = C.launches(lambda: net(x, **kw), ("eegclip_convbncat16_in_width",),
+                                {CAT: lambda d, stream: ((d.KH, d.KW, d.stride, d.pad_h, d.pad_w, d.Cout), (d.out, d.out_c0, d.Cout, d.out_stride)),
+                                 MAXCAT: lambda *a: (None, (a[1], a[9], a[5], a[8]))})
+    return seen, [conv for n, (conv, _) in rec if n == CAT], [part for _, (_, part) in rec], out
 
 
 def expected_launches(blocks):
@@ -97,7 +75,6 @@ def check_features(device, H, W, N, dtype, blocks=FULL, extras=True):
     yardstick that differs; run-to-run bit identity, the launch list, the slices, a batch split into chunks, state-dict loading, transform_input, the bad inputs.
     Returns product error / yardstick error."""
     from eeg_image_decode_amd import metric_nets
-    from eeg_image_decode_amd._lib import EegclipError
     net, x, ref, peak, yard = net_and_refs(device, H, W, N, dtype, blocks)
     pos, ey = float((ref > 0).double().mean()), MR.rel_l2(yard, ref)
     print(f"\n[inception] {blocks} {H}x{W} N={N} {dtype}: largest activation of the fp64 chain {peak:.1f}, {100 * pos:.1f} % of avgpool positive, yardstick {ey:.2e}", end=" ")
@@ -128,14 +105,9 @@ def check_features(device, H, W, N, dtype, blocks=FULL, extras=True):
     res = net.load_state_dict(dict(sd, **{"fc.weight": torch.zeros(4, 8), "fc.bias": torch.zeros(4), "AuxLogits.conv0.conv.weight": torch.zeros(2, 2, 1, 1),
                                           "AuxLogits.fc.bias": torch.zeros(3)}))
     assert not res.missing_keys and not res.unexpected_keys and "Conv2d_1a_3x3.bn.num_batches_tracked" in sd
-    for bad in (dict(sd, **{"Mixed_5b.branch1x1.conv.weight": torch.zeros(1)}), {k: v for k, v in sd.items() if k != "Mixed_6a.branch3x3.bn.running_var"},
-                dict(sd, **{"avgpool.weight": torch.zeros(1)}), {"module." + k: v for k, v in sd.items()},
-                {k: v for k, v in sd.items() if k != "Mixed_7a.branch7x7x3_4.conv.weight"}):
-        try:
-            net.load_state_dict(bad)
-        except RuntimeError:
-            continue
-        raise AssertionError("a wrong key loaded")
+    C.wrong_keys_raise(net, (dict(sd, **{"Mixed_5b.branch1x1.conv.weight": torch.zeros(1)}), {k: v for k, v in sd.items() if k != "Mixed_6a.branch3x3.bn.running_var"},
+                             dict(sd, **{"avgpool.weight": torch.zeros(1)}), {"module." + k: v for k, v in sd.items()},
+                             {k: v for k, v in sd.items() if k != "Mixed_7a.branch7x7x3_4.conv.weight"}))
     net.load_state_dict(sd)
     assert torch.equal(net(x), got)
     # transform_input: without it the result differs; on input transformed beforehand (the product's fp32 a x + b, one rounding) it is the same bit for bit
@@ -144,13 +116,7 @@ def check_features(device, H, W, N, dtype, blocks=FULL, extras=True):
     a, b = (t.to(device) for t in R.affine(True))
     pre = (x.float() * a[None, :, None, None] + b[None, :, None, None]).to(dtype)
     assert not torch.equal(plain(x), got) and torch.equal(plain(pre), got)
-    for bad in (lambda: net(x.to(torch.float32)), lambda: net(x[:, :2]), lambda: net(x[0]), lambda: net(x, chunk=0), lambda: net(x[:0]), lambda: net(x[:, :, :74]),
-                lambda: net(x[:, :, :, :74]), lambda: net(x.to(torch.bfloat16 if dtype == torch.float16 else torch.float16))):
-        try:
-            bad()
-        except EegclipError:
-            continue
-        raise AssertionError("no EegclipError")
+    C.bad_inputs_raise(net, x, dtype, (x[:, :, :74], x[:, :, :, :74]))
     return e / ey
 
 
@@ -192,13 +158,4 @@ def check_table(device, images, recons, net, size, **rows):
     """metrics.reconstruction_metrics(..., inception=net) adds exactly the key "Inception" -- inception_two_way's at its default size -- and leaves the rows of
     the call without it equal; a feature net may not take that name"""
     from eeg_image_decode_amd import metrics as M
-    from eeg_image_decode_amd._lib import EegclipError
-    base = M.reconstruction_metrics(images, recons, size=size, device=device, **rows)
-    out = M.reconstruction_metrics(images, recons, size=size, device=device, inception=net, **rows)
-    assert sorted(out) == sorted(list(base) + ["Inception"]) and all(out[k] == base[k] for k in base)
-    assert isinstance(out["Inception"], float) and out["Inception"] == M.inception_two_way(images, recons, net)
-    try:
-        M.reconstruction_metrics(images, recons, size=size, device=device, inception=net, feature_nets={"Inception": lambda t: t})
-    except EegclipError:
-        return out
-    raise AssertionError("a feature net took the Inception row's name")
+    return C.check_table("Inception", "inception", M.inception_two_way, device, images, recons, net, size, **rows)[1]

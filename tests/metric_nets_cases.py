@@ -8,9 +8,10 @@ import numpy as np
 import torch
 
 import metric_nets_ref as R
+import net_cases as C
 import recon_metrics_ref as RM
+from net_cases import MARGIN
 
-MARGIN = 2.0
 _refs = {}
 
 
@@ -27,23 +28,8 @@ def net_and_refs(device, H, W, N, dtype):
 
 
 def launches(net, x):
-    """the C-ABI launches of one forward, in order, seen through a proxy in front of the library (metric_nets fetches it per call)"""
-    import eeg_image_decode_amd.metric_nets as MN
-    real, seen = MN.lib, []
-
-    class Recording:
-        def __getattr__(self, name):
-            fn = getattr(real(), name)
-            if name == "eegclip_convrelu16_in_width":         # (host arithmetic, no launch)
-                return fn
-            seen.append(name)
-            return fn
-    MN.lib = lambda: Recording()
-    try:
-        net(x)
-    finally:
-        MN.lib = real
-    return seen
+    """the C-ABI launches of one forward, in order"""
+    return C.launches(lambda: net(x), ("eegclip_convrelu16_in_width",))[0]
 
 
 def check_features(device, H, W, N, dtype):
@@ -83,19 +69,10 @@ def check_features(device, H, W, N, dtype):
     assert not torch.equal(zeroed, got["features.11"])                    # (the packed weights and biases follow the load)
     net.load_state_dict(sd)
     assert torch.equal(net(x)["features.11"], got["features.11"])
-    for bad in (dict(sd, **{"features.12.weight": torch.zeros(1)}), {k: v for k, v in sd.items() if k != "features.6.bias"}, dict(sd, **{"avgpool.weight": torch.zeros(1)})):
-        try:
-            net.load_state_dict(bad)
-        except RuntimeError:
-            continue
-        raise AssertionError("a wrong key loaded")
-    for bad in (lambda: net(x[:, :, :30]), lambda: net(x[:, :, :, :14], nodes=("features.4",)), lambda: net(x.to(torch.float32)), lambda: net(x, nodes=("features.12",)),
-                lambda: net(x[:, :2])):
-        try:
-            bad()
-        except EegclipError:
-            continue
-        raise AssertionError("no EegclipError")
+    C.wrong_keys_raise(net, (dict(sd, **{"features.12.weight": torch.zeros(1)}), {k: v for k, v in sd.items() if k != "features.6.bias"},
+                             dict(sd, **{"avgpool.weight": torch.zeros(1)})))
+    C.all_raise(EegclipError, (lambda: net(x[:, :, :30]), lambda: net(x[:, :, :, :14], nodes=("features.4",)), lambda: net(x.to(torch.float32)),
+                               lambda: net(x, nodes=("features.12",)), lambda: net(x[:, :2])), "no EegclipError")
     small = net(x[:, :, :15, :16], nodes=("features.4",))["features.4"]   # the smallest input of the shallow node
     assert tuple(small.shape) == (N, 192, 1, 1)
     return ratios
@@ -142,9 +119,5 @@ def check_table(device, images, recons, net, size):
     """metrics.reconstruction_metrics(..., alexnet=net): the four keys, the AlexNet rows are alexnet_two_way's at its default size, and PixCorr / SSIM are
     those of the call without a net"""
     from eeg_image_decode_amd import metrics as M
-    base = M.reconstruction_metrics(images, recons, size=size, device=device)
-    out = M.reconstruction_metrics(images, recons, size=size, device=device, alexnet=net)
+    base, out = C.check_table(None, "alexnet", M.alexnet_two_way, device, images, recons, net, size)
     assert sorted(base) == ["PixCorr", "SSIM"] and sorted(out) == ["AlexNet(2)", "AlexNet(5)", "PixCorr", "SSIM"]
-    assert out["PixCorr"] == base["PixCorr"] and out["SSIM"] == base["SSIM"]
-    rows = M.alexnet_two_way(images, recons, net)
-    assert all(isinstance(out[k], float) and out[k] == rows[k] for k in rows)

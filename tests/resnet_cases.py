@@ -4,14 +4,13 @@ metric_nets.ResNetFeatures, metrics.correlation_distance / swav_distance against
 The network bound is tests/metric_nets_cases.py's: the relative L2 distance of `avgpool` to the fp64 restatement is at most 2 x the yardstick's own -- the same
 chain in fp32 with the input, the weights and every launch's output rounded to the dtype, on the same inputs and weights.  That is what any 16-bit
 implementation pays; the factor 2 covers a different accumulation order and that two sets of random roundings do not coincide."""
-import numpy as np
 import torch
 
 import metric_nets_ref as MR
+import net_cases as C
 import resnet_ref as R
+from net_cases import MARGIN
 
-MARGIN = 2.0
-CORR_BOUND = 64 * 2.0 ** -24                    # tests/test_kernels_resnet.py: eegclip_corr_distance against scipy
 FULL, SHALLOW = (3, 4, 6, 3), (1, 1, 1, 1)
 _refs = {}
 
@@ -29,36 +28,15 @@ def net_and_refs(device, H, W, N, dtype, layers):
 
 
 def launches(net, x, **kw):
-    """-> (the C-ABI launches of one forward, in order, seen through a proxy in front of the library (metric_nets fetches it per call); for eegclip_convbn16
-    also (KS, stride, relu, has a residual); the forward's result)"""
-    import eeg_image_decode_amd.metric_nets as MN
-    real, seen, convs = MN.lib, [], []
-
-    class Recording:
-        def __getattr__(self, name):
-            fn = getattr(real(), name)
-            if name == "eegclip_convbn16_in_width":            # (host arithmetic, no launch)
-                return fn
-            seen.append(name)
-            if name != "eegclip_convbn16":
-                return fn
-
-            def conv(d, stream):
-                convs.append((d.KS, d.stride, d.relu, d.residual is not None))
-                return fn(d, stream)
-            return conv
-    MN.lib = lambda: Recording()
-    try:
-        out = net(x, **kw)
-    finally:
-        MN.lib = real
-    return seen, convs, out
+    """-> (the C-ABI launches of one forward, in order; for eegclip_convbn16 also (KS, stride, relu, has a residual); the forward's result)"""
+    seen, rec, out = C.launches(lambda: net(x, **kw), ("eegclip_convbn16_in_width",),
+                                {"eegclip_convbn16": lambda d, stream: (d.KS, d.stride, d.relu, d.residual is not None)})
+    return seen, [v for _, v in rec], out
 
 
 def check_features(device, H, W, N, dtype, layers=FULL, extras=True):
     """`avgpool` against the fp64 restatement within 2 x the yardstick; from the reference alone: no activation near fp16's range and a live node; run-to-run bit
     identity, the launch list, a batch split into chunks, state-dict loading, the bad inputs, the smallest image.  Returns product error / yardstick error."""
-    from eeg_image_decode_amd._lib import EegclipError
     net, x, ref, peak, yard = net_and_refs(device, H, W, N, dtype, layers)
     pos = float((ref > 0).double().mean())
     print(f"\n[resnet] {layers} {H}x{W} N={N} {dtype}: largest activation of the fp64 chain {peak:.1f}, {100 * pos:.1f} % of avgpool positive", end=" ")
@@ -91,75 +69,25 @@ def check_features(device, H, W, N, dtype, layers=FULL, extras=True):
                  "module.prototypes.weight": torch.zeros(4, 8)})
     res = net.load_state_dict(full)
     assert not res.missing_keys and not res.unexpected_keys
-    for bad in (dict(sd, **{"layer1.0.conv4.weight": torch.zeros(1)}), {k: v for k, v in sd.items() if k != "layer2.0.downsample.1.running_var"},
-                dict(sd, **{"avgpool.weight": torch.zeros(1)}), {"backbone." + k: v for k, v in sd.items()}):
-        try:
-            net.load_state_dict(bad)
-        except RuntimeError:
-            continue
-        raise AssertionError("a wrong key loaded")
+    C.wrong_keys_raise(net, (dict(sd, **{"layer1.0.conv4.weight": torch.zeros(1)}), {k: v for k, v in sd.items() if k != "layer2.0.downsample.1.running_var"},
+                             dict(sd, **{"avgpool.weight": torch.zeros(1)}), {"backbone." + k: v for k, v in sd.items()}))
     net.load_state_dict(sd)
     assert torch.equal(net(x), got)
-    for bad in (lambda: net(x.to(torch.float32)), lambda: net(x[:, :2]), lambda: net(x[0]), lambda: net(x, chunk=0), lambda: net(x[:0]), lambda: net(x[:, :, :0]),
-                lambda: net(x.to(torch.bfloat16 if dtype == torch.float16 else torch.float16))):
-        try:
-            bad()
-        except EegclipError:
-            continue
-        raise AssertionError("no EegclipError")
+    C.bad_inputs_raise(net, x, dtype, (x[:, :, :0],))
     return e / ey
 
 
 def check_smallest(device, dtype, layers=SHALLOW):
-    """MIN_SIDE = 1: a 1 x 1 and a 1 x 2 image reach `avgpool` and meet the same bound"""
-    from eeg_image_decode_amd import metric_nets
-    assert metric_nets.MIN_SIDE == 1
-    for H, W in ((1, 1), (1, 2)):
-        net, x, ref, peak, yard = net_and_refs(device, H, W, 2, dtype, layers)
-        got = net(x)
-        e, ey = MR.rel_l2(got, ref), MR.rel_l2(yard, ref)
-        print(f"\n[resnet] {layers} {H}x{W} {dtype}: rel L2 {e:.2e}, yardstick {ey:.2e}", end=" ")
-        assert tuple(got.shape) == (2, 2048) and ey > 0 and e <= MARGIN * ey
+    C.check_smallest("resnet", net_and_refs, device, dtype, layers, 2048)
 
 
 def check_swav_row(device, H, W, N, layers=FULL, dtype=torch.float16):
-    """metrics.swav_distance at H x W (size=H: no resize) on R.mixed_pairs: bit for bit correlation_distance of the net's features of both sides, its mean their
-    mean, and each distance within the corr_distance bound of scipy's on the product's own features.  From the reference alone, first: every reference distance
-    is at least 10 x what the yardstick's rounding moves it by.  Returns (images, recons, net)."""
+    """C.check_distance_row for metrics.swav_distance.  Returns (images, recons, net)."""
     from eeg_image_decode_amd import metric_nets, metrics as M, preprocess as P
-    images, recons = (t.to(device) for t in MR.mixed_pairs(N, H, W))
-    net = metric_nets.ResNetFeatures(layers=layers, dtype=dtype, device=device, seed=0)
-    pre = lambda t: P.swav_preprocess(t, size=H, dtype=dtype, device=device, in_range=(0.0, 1.0))   # noqa: E731
-    xa, xb = pre(images), pre(recons)
-    assert tuple(xa.shape) == (N, 3, H, W)
-    sd = net.state_dict()
-    (fa, _), (fb, _) = R.features(xa, sd, layers), R.features(xb, sd, layers)
-    d_ref, d_yard = R.correlation(fa, fb), R.correlation(R.yardstick(xa, sd, layers, dtype), R.yardstick(xb, sd, layers, dtype))
-    moved = float(np.abs(d_yard - d_ref).max())
-    print(f"\n[resnet] SwAV row {layers} {H}x{W} N={N}: reference distances {d_ref.min():.2e} .. {d_ref.max():.2e}, {dtype} rounding moves them by {moved:.1e}", end=" ")
-    assert (d_ref >= 10 * moved).all(), (d_ref, moved)
-    mean, d = M.swav_distance(images, recons, net, size=H, return_distances=True)
-    ga, gb = net(xa), net(xb)
-    assert d.dtype == torch.float32 and tuple(d.shape) == (N,) and d.device.type == torch.device(device).type
-    assert torch.equal(d, M.correlation_distance(ga, gb)) and mean == float(d.mean()) and isinstance(mean, float)
-    assert M.swav_distance(images, recons, net, size=H) == mean
-    own = R.correlation(ga, gb)
-    err = float(np.abs(d.cpu().double().numpy() - own).max())
-    print(f"\n[resnet] SwAV row: max |d - scipy on the same features| {err:.2e} = {err * 2 ** 24:.1f} x 2^-24", end=" ")
-    assert err <= CORR_BOUND
-    return images, recons, net
+    return C.check_distance_row("resnet", "SwAV", R, metric_nets.ResNetFeatures, P.swav_preprocess, M.swav_distance, device, H, W, N, layers, dtype)
 
 
 def check_table(device, images, recons, net, size, alexnet=None):
     """metrics.reconstruction_metrics(..., swav=net): the key "SwAV" is swav_distance's at its default size, the other rows are those of the call without it"""
     from eeg_image_decode_amd import metrics as M
-    from eeg_image_decode_amd._lib import EegclipError
-    base = M.reconstruction_metrics(images, recons, size=size, device=device, alexnet=alexnet)
-    out = M.reconstruction_metrics(images, recons, size=size, device=device, alexnet=alexnet, swav=net)
-    assert sorted(out) == sorted(list(base) + ["SwAV"]) and all(out[k] == base[k] for k in base)
-    assert isinstance(out["SwAV"], float) and out["SwAV"] == M.swav_distance(images, recons, net)
-    try:
-        M.reconstruction_metrics(images, recons, size=size, device=device, swav=net, feature_nets={"SwAV": lambda t: t})
-    except EegclipError:
-        return out
-    raise AssertionError("a feature net took the SwAV row's name")
+    return C.check_table("SwAV", "swav", M.swav_distance, device, images, recons, net, size, alexnet=alexnet)[1]

@@ -24,8 +24,8 @@ sys.path.insert(0, ROOT)
 from bench_clip_vision import spread, update_json, window_us  # noqa: E402
 
 SIZE, CHUNK, WARMUP = 342, 64, 2
-FAMILIES = (("conv", "convrelu16_kernel"), ("avgpool3x3", "avgpool3x3_16_kernel"), ("maxpool_branch", "maxpool16_cat_kernel"), ("maxpool_stem", "maxpool16_kernel"),
-            ("avgpool", "avgpool16_kernel"), ("pack", "pack_nchw16_affine_kernel"))
+FAMILIES = (("conv", "convrelu16_kernel"), ("avgpool3x3", "avgpool3x3_16_kernel"), ("maxpool", "maxpool16_kernel"), ("avgpool", "avgpool16_kernel"),
+            ("pack", "pack_nchw16_kernel"))          # (the stem's max-pools and the max-pool branches are one kernel)
 
 
 def useful_flops(net, size=SIZE):
